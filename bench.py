@@ -24,9 +24,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# (the same default unopose_amd/__init__.py sets, here because this process touches the GPU before it imports the package: the runner
-#  uses up to nine streams, the HIP runtime maps them onto 4 hardware queues by default and streams sharing a queue serialise)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 
 def parse(argv=None):
@@ -64,6 +61,10 @@ def parse(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="TEST HOOK (tests/test_bench_cpu.py): replace the model step by a host stub so that the launch / "
                          "rendezvous / barrier / gather / JSON path runs without a GPU (backend gloo); never a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its LAST step (forward: the keys the forward "
+                         "adds to end_points; --train: the step's loss terms) as DIR/<name>.npy in float32 / float64, rank 0 only, "
+                         "at most 64 MB in all.  Inputs are seeded, so two builds run with the same arguments compare output for output")
     return ap.parse_args(argv)
 
 
@@ -99,6 +100,38 @@ _T0 = time.perf_counter()
 def log(msg):
     """Progress on stderr (stdout carries only the JSON line)."""
     print("[bench %7.1fs] %s" % (time.perf_counter() - _T0, msg), file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET = 64 << 20  # bytes, all arrays of one --dump-outputs together
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: tensor} as dirname/<name>.npy: float64 stays float64, every other dtype becomes float32 (integer indices
+    above 2^24 as float64, so they stay exact).  If the whole exceeds DUMP_BUDGET, each array is replaced by a fixed, seeded
+    sample of its flattened elements (sorted indices, the same for every run of the same shapes).  -> {name: shape written}."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, t in sorted(arrays.items()):
+        t = torch.as_tensor(t).detach().cpu()
+        if t.dtype == torch.float64 or (not t.is_floating_point() and t.dtype != torch.bool and t.numel() and t.abs().max().item() >= 2 ** 24):
+            host[name] = t.double().numpy()
+        else:
+            host[name] = t.float().numpy()
+    total = sum(a.nbytes for a in host.values())
+    room = DUMP_BUDGET - 1024 * len(host)  # each .npy header takes 128 bytes or so
+    written = {}
+    for name, a in host.items():
+        if total > room:
+            keep = max(1, a.size * room // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = list(a.shape)
+    log("outputs of the last timed step written to %s: %s" % (dirname, ", ".join(written)))
+    return written
 
 
 def hip_event_time(fn, iters, stream, warm=1):
@@ -555,10 +588,12 @@ def train_main(args, world, rank, dev, sync):
     opt, sched = build_optimizer(model, lr=1e-4, total_iters=188340)
     amp = torch.bfloat16 if args.train_dtype == "bf16" else None
     losses = []
+    last = {}
 
     def step():
         info = train_step(net, batch, opt, sched, amp_dtype=amp)
         losses.append(info["loss"])
+        last.update(info)
 
     log("model + batch ready (rank %d of %d)" % (rank, world))
     for _ in range(args.warmup):
@@ -607,6 +642,8 @@ def train_main(args, world, rank, dev, sync):
     }
     if per_rank is not None:
         res["per_rank_ms_per_step"] = per_rank
+    if rank == 0 and args.dump_outputs:
+        res["dumped_outputs"] = dump_outputs(args.dump_outputs, {k: v for k, v in last.items() if hasattr(v, "shape")})
     if rank == 0:
         print(json.dumps(res), flush=True)
     if world > 1:
@@ -755,6 +792,9 @@ def main():
         per_rank = [[float(v) for v in e.tolist()] for e in every]
 
     log("timed region done: %.2f ms/step" % (dt / args.steps * 1e3))
+    dumped = None
+    if rank == 0 and args.dump_outputs:  # what the forward added to the caller's end_points (poses and scores)
+        dumped = dump_outputs(args.dump_outputs, {k: v for k, v in out.items() if k not in batch and hasattr(v, "shape")})
     rot_err = (out["pred_R"] - R_gt).abs().amax(dim=(1, 2))
     res = {
         "metric": "(query,ref) pairs/sec forward",
@@ -789,6 +829,8 @@ def main():
                                       "slowest rank); no collective on the data path"}
     if args.dry_run:
         res["dry_run"] = True
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
     if pipe is not None:
         # HIP events of every step: start / end on the stream it ran on.  `step_ms_hip_events` = time between the completions of
         # steps i and i + depth (two consecutive steps of ONE stream), divided by depth: the per-step period of the pipeline

@@ -1,5 +1,5 @@
 """One bench run with a module attribute / environment knob set: python scripts/ubench/knob_ab.py <img> name=value ...
-names: model.GEOM_UNDER_VIT=2, env.GPU_MAX_HW_QUEUES=24, ops.SOMETHING=False, pipeline.WHOLE_INTERNAL_OVERLAP=False"""
+names: model.GEOM_UNDER_VIT=2, env.<VARIABLE>=<value>, ops.SOMETHING=False, pipeline.WHOLE_INTERNAL_OVERLAP=False"""
 import io, json, os, sys
 from contextlib import redirect_stdout
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -39,3 +39,21 @@ def test_bench_single_rank_dry_run_and_world_mismatch():
     # a launcher-provided WORLD_SIZE that disagrees with --gpus is refused (never a 1-rank number labelled 8 GPUs)
     r = _run(["--gpus", "8", "--dry-run"], env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "refusing" in r.stderr
+
+
+def test_bench_dump_outputs_writes_the_last_step_and_repeats(tmp_path):
+    import numpy as np
+
+    runs = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r = _run(["--steps", "3", "--warmup", "1", "--batch", "4", "--dry-run", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = json.loads(r.stdout.strip().splitlines()[-1])
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        assert set(res["dumped_outputs"]) == {"pred_R", "pred_t", "pred_pose_score"}
+        runs.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    assert set(runs[0]) == {"pred_R", "pred_t", "pred_pose_score"}
+    assert runs[0]["pred_R"].shape == (4, 3, 3) and runs[0]["pred_R"].dtype == np.float32
+    for k, v in runs[0].items():
+        assert np.array_equal(v, runs[1][k]), k

@@ -86,16 +86,3 @@ def test_shared_reference_batch_is_consistent_geometry():
         assert set(ep["rgb_choose"][b].tolist()) <= set(ep["tem1_choose"][b].tolist())
     assert (R @ R.transpose(1, 2) - torch.eye(3)).abs().max().item() < 1e-5
 
-
-def test_package_import_defaults_the_hardware_queue_count_without_overriding_the_user():
-    import os
-    import subprocess
-    import sys
-
-    code = "import os, unopose_amd; print(os.environ['GPU_MAX_HW_QUEUES'])"
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
-    env["PYTHONPATH"] = root
-    assert subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True).stdout.strip() == "16"
-    env["GPU_MAX_HW_QUEUES"] = "2"
-    assert subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True).stdout.strip() == "2"

@@ -24,7 +24,7 @@ import torch
 from . import ops
 
 
-# HIP streams are a process-wide resource that maps onto a handful of hardware queues (GPU_MAX_HW_QUEUES = 4 by default): every stream
+# HIP streams are a process-wide resource that maps onto a handful of hardware queues (4 by default): every stream
 # a process has EVER created keeps its queue assignment, and two streams that share a queue serialise.  A process that builds one pipeline
 # after another (bench.py's legs, a runner that is re-created per dataset) must therefore not mint new streams each time -- measured in
 # round 6: the bounded training leg at the end of bench.py's default run took 119 ms per step against 108 ms in a process of its own, its
@@ -101,9 +101,9 @@ class PipelinedForward:
         self._pending = collections.deque()
         # run_ahead: forwards the host may enqueue beyond `depth` before it has seen one finish.  Default 1 with several forwards in
         # flight; 0 with ONE forward at a time (fp32): there the next forward's first side-stream wait, enqueued a whole forward early,
-        # can share a hardware queue with the running forward's stream (HIP multiplexes streams onto GPU_MAX_HW_QUEUES = 4 queues) --
+        # can share a hardware queue with the running forward's stream (HIP multiplexes streams onto 4 queues by default) --
         # measured 87 -> 101 ms per fp32 forward whenever the stream pool happened to be laid out that way (bf16 stage-mode steps earlier
-        # in the process; GPU_MAX_HW_QUEUES=8 also cures it), against 1 % for giving up the run-ahead.
+        # in the process; 8 hardware queues also cure it), against 1 % for giving up the run-ahead.
         if run_ahead is None:
             run_ahead = 1 if self.depth > 1 else 0
         self._limit = self.depth + max(0, int(run_ahead))  # forwards the host may have enqueued and not yet seen finish
