@@ -1,6 +1,6 @@
 // ROUND 6 EXPERIMENT, NOT IN THE LIBRARY (csrc/attn.hip with one more kernel, `token_attn_rpe_t_kernel`, and its dispatch; build it in place of
-// csrc/attn.hip with  python scripts/build_variant.py tat attn.hip=scripts/ubench/attn_rpe_transposed.hip [-DTA_ROWS_T_VAL=4|8|12|16]
-// and time it with  UNOPOSE_LIB=unopose_amd/libunopose_hip_tat.so python scripts/ubench/rpe_time.py).
+// csrc/attn.hip of commit 3ad6ca8, whose scripts/build_variant.py did that [-DTA_ROWS_T_VAL=4|8|12|16], and time it with
+// UNOPOSE_LIB=<that library> python scripts/ubench/rpe_time.py).
 // The verdict's design for the RPE token attention -- scores computed transposed, P kept in registers (no LDS staging, no barrier), V^T read in the
 // permuted key order, the embedding stream running on across the wave's row tiles -- built and correct on its first run (max error against the fp32
 // composite 6.5e-4, as round 5's kernel), and SLOWER: 313.6 us at 64 x 197 x 197 x 256 against 291.5 us, with 4 rows per wave (no stream carry-over)

@@ -10,7 +10,7 @@ import os
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# UNOPOSE_LIB: an alternative build of the SAME library (scripts/build_variant.py: same sources, other compiler flags) for same-box A/Bs
+# UNOPOSE_LIB: another build of the SAME library (e.g. the parent commit's sources) for same-box A/Bs and output comparisons
 SO_PATH = os.environ.get("UNOPOSE_LIB") or os.path.join(_HERE, "libunopose_hip.so")
 
 _lib = None

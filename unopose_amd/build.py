@@ -21,13 +21,12 @@ ARCH = "gfx950"
 # isolated by re-assembling the ISA, scripts/ubench/asm_var.py) return wrong values for a few elements per
 # launch whenever waves of ANOTHER kernel issuing MFMAs share their CU -- 23 of 30 launches beside a neighbour that does nothing but
 # v_mfma, 0 of 30 when built with this flag or at -O1, and never beside VALU / LDS / memory / barrier neighbours
-# (scripts/ubench/coresidency_matrix.py, geom_var.py; the loop vectoriser forms a few more, hence both flags).
+# (scripts/ubench/coresidency_matrix.py; the loop vectoriser forms a few more, hence both flags).
 # Packed fp32 brings no throughput on gfx950, so the
 # flags cost nothing (898 vs 892 pairs/s, inside the run-to-run spread).  tests/test_abi.py compiles every source to ISA with
 # these flags and fails if a packed-fp32 instruction is left.
-# UNOPOSE_EXTRA_HIPCC_FLAGS come LAST (the last -O wins) and are part of the staleness key below: a changed value rebuilds everything.
 FLAGS = ["-O3", "-fno-slp-vectorize", "-fno-vectorize", "-std=c++17", "-fPIC", "-ffp-contract=off",
-         f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", *os.environ.get("UNOPOSE_EXTRA_HIPCC_FLAGS", "").split()]
+         f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 # Dense-math kernels: `nnan` lets fmaxf lower to ONE v_max_f32 instead of canonicalise + max (the PE tile
 # loop had 288 v_max for 112 logical maxima).  Not applied to the index-producing files (pointnet2, geom,
 # posehead), whose NaN behaviour follows the reference's fminf / fmaxf semantics.

@@ -23,19 +23,13 @@ __device__ __forceinline__ u16 f2bf_rn(float f) {
   return (u16)(u >> 16);
 }
 
-#ifndef TA_DPP_BUTTERFLY
-#define TA_DPP_BUTTERFLY 1  // 0: the butterfly through ds_swizzle (LDS crossbar); see DESIGN.md section 7
-#endif
 template <int XOR>
 __device__ __forceinline__ float swz_xor(float v) {  // butterfly step inside a 16-lane row, no LDS memory touched
-#if TA_DPP_BUTTERFLY
+  // (DPP rather than ds_swizzle through the LDS crossbar: DESIGN.md section 7)
   // DPP: quad_perm [1,0,3,2] / [2,3,0,1] for xor 1 / 2; row_half_mirror / row_mirror for xor 4 / 8 -- applied in this order every
   // lane's partner group holds the value the xor partner would (the groups are uniform by then), so sums and maxima are unchanged
   constexpr int ctrl = XOR == 1 ? 0xB1 : XOR == 2 ? 0x4E : XOR == 4 ? 0x141 : 0x140;
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, false));
-#else
-  return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (XOR << 10) | 0x1F));
-#endif
 }
 __device__ __forceinline__ float row16_max(float v) {
   v = fmaxf(v, swz_xor<1>(v));
@@ -224,9 +218,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_kernel(const u16 *__restric
 // reads them): no barriers, only its own counted vmcnt -- the tile after next is issued as soon as the current one has been read, so
 // one to two tiles (8 - 16 KiB per wave, 64 - 128 KiB per CU) are in flight all the time.  Same MFMA order as token_attn_kernel<true>:
 // bit-identical results.
-#ifndef TA_EPOL
-#define TA_EPOL 1  // cache policy of the embedding stream's LDS-DMA loads (gemm_dma16<POL>: 0 default, 1 nt, 2 sc1, 3 sc0 sc1 nt).  The stream (1.27 GB per launch, read once) no longer pushes K / V^T -- re-read by every wave of a cloud -- out of L2: 291.5 -> 272.5 us at 64 x 197 x 197 x 256 (nt), 291 (sc1), 272 (sc0 sc1 nt); round 6
-#endif
+constexpr int TA_EPOL = 1;  // cache policy of the embedding stream's LDS-DMA loads (gemm_dma16<POL>: 0 default, 1 nt, 2 sc1, 3 sc0 sc1 nt).  The stream (1.27 GB per launch, read once) no longer pushes K / V^T -- re-read by every wave of a cloud -- out of L2: 291.5 -> 272.5 us at 64 x 197 x 197 x 256 (nt), 291 (sc1), 272 (sc0 sc1 nt); round 6
 constexpr int TA_RING = 2 * 8192;  // per wave
 constexpr int TA_ROWS = 4;         // query rows per wave, processed in MFMA tiles of 4.  Measured at 64 x 197 x 197: 4 rows 290 us, 7 rows (4 + 3:
                                    // every wave task in ONE round of the 2048 wave slots) 305 us -- the kernel is bound by bytes in flight x latency, and
@@ -422,11 +414,7 @@ int unopose_token_attention(const void *q, int ldq, const void *k, int ldk, cons
                   "token_attention: row strides must be multiples of 8 elements (16-byte loads)");
   if (B == 0) return UNOPOSE_OK;
   hipStream_t s = (hipStream_t)stream;
-  bool dma = E && (size_t)B * n * m * 512 < (1UL << 32);   // (32-bit LDS-DMA offsets; larger embeddings: the fragment-load kernel)
-#ifdef UNOPOSE_PROBE_BUILD
-  static const bool ta_old = getenv("UNOPOSE_TA_OLD") != nullptr;   // A/B: round 4's fragment-load kernel
-  dma = dma && !ta_old;
-#endif
+  const bool dma = E && (size_t)B * n * m * 512 < (1UL << 32);   // (32-bit LDS-DMA offsets; larger embeddings: the fragment-load kernel)
   if (dma) {
     static bool opt[64];
     if (lds_optin(opt, (const void *)token_attn_rpe_dma_kernel, 4 * TA_RING, "token_attention") != UNOPOSE_OK) return UNOPOSE_ELAUNCH;

@@ -52,9 +52,7 @@ __device__ __forceinline__ float af_swz(float v) {
 }
 
 constexpr int AF_NT = 14, AF_MP = AF_NT * 16;
-#ifndef AF_PF_DEPTH
-#define AF_PF_DEPTH 4  // operand pairs in flight ahead of the MFMAs of the token attention
-#endif
+constexpr int AF_PF_DEPTH = 4;  // operand pairs in flight ahead of the MFMAs of the token attention
 
 // ---- token attention (see attn.hip for the scheme): one wave = 4 query rows x 4 heads ----------------
 template <bool RPE>

@@ -90,9 +90,6 @@ __device__ __forceinline__ int ge_swz(int row, int kbyte) {
   return row * 512 + (kbyte ^ ((row & 15) << 4));
 }
 
-#ifndef GE_PIN
-#define GE_PIN 0  // 1 (measured, not kept): fragment reads batched and pinned ahead of the MFMAs -- 95 -> 138 VGPRs (5 -> 3 waves per SIMD): bf16 step -2 %, fp32 step +0.3 %
-#endif
 template <bool SPLIT, bool OUT_BF16>
 __global__ __launch_bounds__(GE_THREADS) void geo_embed_kernel(
     const float *__restrict__ pts, const int32_t *__restrict__ knn, const u16 *__restrict__ wd_hi,
@@ -217,27 +214,8 @@ __global__ __launch_bounds__(GE_THREADS) void geo_embed_kernel(
         rbal[slot] = Wa_lo[(ks + PF) * 512];
       }
     }
-#if GE_PIN
-    // all A fragments of the k-step read as one batch, and neither they nor the ring's loads above may sink below this point: hipcc
-    // otherwise moves every read next to its MFMAs (the 4-deep ring arrived in the ISA as `s_waitcnt vmcnt(1)` right behind the loads)
-    bf16x8 af[4], afl[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      af[s] = *reinterpret_cast<const bf16x8 *>(Ahi + ge_swz(s * GE_PAIRS + arow, kidx * 16));
-      if (SPLIT) afl[s] = *reinterpret_cast<const bf16x8 *>(Alo + ge_swz(s * GE_PAIRS + arow, kidx * 16));
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const bf16x8 bw = s == 0 ? bd : ba;
-      acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s], bw, acc[s], 0, 0, 0);
-      if (SPLIT) {
-        const bf16x8 bl = s == 0 ? bdl : bal;
-        acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s], bl, acc[s], 0, 0, 0);
-        acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afl[s], bw, acc[s], 0, 0, 0);
-      }
-    }
-#else
+    // (measured and not kept: the A fragments of the k-step read as one batch pinned ahead of the MFMAs -- 95 -> 138 VGPRs, 5 -> 3 waves per
+    //  SIMD: bf16 step -2 %, fp32 step +0.3 %)
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const bf16x8 a = *reinterpret_cast<const bf16x8 *>(Ahi + ge_swz(s * GE_PAIRS + arow, kidx * 16));
@@ -250,7 +228,6 @@ __global__ __launch_bounds__(GE_THREADS) void geo_embed_kernel(
         acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bw, acc[s], 0, 0, 0);
       }
     }
-#endif
   }
 
   // ---------------- phase 3: E = d + reduce_k(a_k) + (b_d + b_a)
@@ -298,9 +275,6 @@ typedef float gt_f4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const gt_f4 gt_lds_f4;
 
 __device__ __forceinline__ float gt_bcast(float v, int l) {
-#if defined(GT_ABL) && GT_ABL == 1   // (timing probe, scripts/ubench/geo_table_abl.cpp: no weight broadcasts)
-  return v;
-#endif
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
 
@@ -414,10 +388,6 @@ __global__ __launch_bounds__(1024) void geo_embed_table_kernel(const float *__re
         gt_lds_f4 *t = (gt_lds_f4 *)(uintptr_t)(lds0 + __builtin_amdgcn_readlane(off[k], l));
 #pragma unroll
         for (int m = 0; m < NP; ++m) dst[m] = t[64 * m];
-#if defined(GT_ABL) && GT_ABL == 2   // (timing probe: no LDS reads)
-#pragma unroll
-        for (int m = 0; m < NP; ++m) dst[m] = gt_f4{(float)(uintptr_t)t, 1.f, 2.f, 3.f};
-#endif
       };
       lds_rows(1, ta);
       if (od >= 0) {
@@ -458,9 +428,6 @@ __global__ __launch_bounds__(1024) void geo_embed_table_kernel(const float *__re
         const float a = MEAN ? (v[1][c] + v[2][c] + v[3][c]) * (1.f / 3.f) : fmaxf(fmaxf(v[1][c], v[2][c]), v[3][c]);
         o[c] = v[0][c] + a + b4[c];
       }
-#if defined(GT_ABL) && GT_ABL == 3   // (timing probe: one store per chunk)
-      if (l != cols - 1 || o[0] == 123.f) continue;
-#endif
       if (OUT_BF16)
         *reinterpret_cast<uint2 *>(orow + (size_t)l * 512) = make_uint2(cvt_pk_bf16(o[0], o[1]), cvt_pk_bf16(o[2], o[3]));
       else

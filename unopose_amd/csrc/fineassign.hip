@@ -22,8 +22,6 @@
 // the swept side (the background token) is the first element of tile 0; index 0 of the owning side belongs to nobody: its
 // statistics are the per-workgroup partial sums the other direction's pass 0 leaves behind plus the corner x_00, summed in
 // a fixed order by whoever needs them (deterministic: no atomics).
-#include <stdlib.h>
-
 #include "common.h"
 
 namespace unopose {
@@ -47,7 +45,6 @@ struct FAParams {
   float *w[2];             // (B, n[d] - 1) labels
   const float *pts2;       // (B, n[1] - 1, 3)
   float *weight, *pred;    // (B, n[0] - 1), (B, n[0] - 1, 3)
-  int old_grid;            // A/B switch (UNOPOSE_FA_OLD_GRID=1): block index fastest, as first written
 };
 
 __device__ __forceinline__ float fa_half_sum(float v) { return v + __shfl_xor(v, 32); }
@@ -61,7 +58,7 @@ __global__ __launch_bounds__(512) void fine_assign_kernel(const FAParams p) {
   const int dir = MODE == 0 ? (int)blockIdx.z : (MODE == 1 ? 1 : 0);
   // grid.x = pair, grid.y = block: workgroup ids of one pair are B apart, i.e. (B % 8 == 0) on ONE XCD -- the 8 owners of a pair
   // re-read the same swept side (1 MB) and share it in that XCD's L2 instead of fetching it 8 times (PMC: 601 -> MB per launch)
-  const int blk = p.old_grid ? blockIdx.x : blockIdx.y, b = p.old_grid ? blockIdx.y : blockIdx.x;
+  const int blk = blockIdx.y, b = blockIdx.x;
   if (blk >= p.nblk[dir]) return;
   const int NO = p.n[dir], NS = p.n[1 - dir];
   const u16 *own = p.f[dir] + (size_t)b * NO * FA_D;
@@ -284,18 +281,6 @@ int unopose_fine_assign(const void *f1, const void *f2, int B, int R, int C, int
       lds_optin(opt2, (const void *)fine_assign_kernel<2>, 150 * 1024, "fine_assign") != UNOPOSE_OK)
     return UNOPOSE_ELAUNCH;
   const int nb = p.nblk[0] > p.nblk[1] ? p.nblk[0] : p.nblk[1];
-#ifdef UNOPOSE_PROBE_BUILD  // (the grid order before the XCD-aware one: A/B in probe builds only)
-  static const int old_grid = getenv("UNOPOSE_FA_OLD_GRID") ? atoi(getenv("UNOPOSE_FA_OLD_GRID")) : 0;
-#else
-  const int old_grid = 0;
-#endif
-  p.old_grid = old_grid;
-  if (old_grid) {
-    hipLaunchKernelGGL(fine_assign_kernel<0>, dim3(nb, B, 2), dim3(512), lds0, s, p);
-    hipLaunchKernelGGL(fine_assign_kernel<1>, dim3(p.nblk[1], B), dim3(512), lds1, s, p);
-    hipLaunchKernelGGL(fine_assign_kernel<2>, dim3(p.nblk[0], B), dim3(512), lds2, s, p);
-    return check_launch("fine_assign");
-  }
   hipLaunchKernelGGL(fine_assign_kernel<0>, dim3(B, nb, 2), dim3(512), lds0, s, p);
   hipLaunchKernelGGL(fine_assign_kernel<1>, dim3(B, p.nblk[1]), dim3(512), lds1, s, p);
   hipLaunchKernelGGL(fine_assign_kernel<2>, dim3(B, p.nblk[0]), dim3(512), lds2, s, p);

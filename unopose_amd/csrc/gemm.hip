@@ -31,8 +31,6 @@
 //     tiles then touch different 128-byte columns of their panels at any instant;
 //   * epilogue on the fp32 accumulators: + bias, optional GELU / ReLU / residual + LayerNorm, bf16, staged through LDS
 //     (XOR-swizzled) and written as whole 128-byte row segments with NON-TEMPORAL stores when the output exceeds the L2s.
-#include <stdlib.h>
-
 #include <mutex>
 
 #include "gemm_kernel.h"
@@ -43,24 +41,16 @@ using namespace unopose;
 // next launch reads them, and a round of tiles would otherwise push the operand panels out of L2.
 static inline int use_nt_store(long M, int N) { return (size_t)M * N * 2 > (32u << 20) ? 1 : 0; }
 
-// Shape policy: when the 256 x 256 tiles cannot give 5 / 8 of the CUs one (`UNOPOSE_GEMM_SMALL_TILES` overrides the limit for A/Bs:
-// scripts/gemm_policy_ab.sh), the GEMM runs on gemm_small.hip's 128 x 128 (64 x 256 with the LayerNorm epilogue) tiles.
+// Shape policy: when the 256 x 256 tiles cannot give 5 / 8 of the CUs one, the GEMM runs on gemm_small.hip's 128 x 128 (64 x 256 with
+// the LayerNorm epilogue) tiles.
 // (Measured and not kept: giving the 256-tile kernel only whole rounds of tiles and the last row panels to the small kernel --
 // fc2 at M = 87 936 is 1032 tiles on 256 CUs -- gains 0 - 3 % per shape, 0.07 ms per forward: the few tiles of a last round
 // already run faster than those of a full one.)
 namespace unopose {
 int gemm_small_tiles_limit() {
-#ifdef UNOPOSE_PROBE_BUILD  // (scripts/gemm_policy_ab.sh: probe builds only)
-  static const int v = [] {
-    const char *e = getenv("UNOPOSE_GEMM_SMALL_TILES");
-    return e && *e ? atoi(e) : -1;
-  }();
-#else
-  const int v = -1;
-#endif
-  // default: below 5/8 of the CUs.  At 77 % fill (198 tiles: the 224 x 224 ViT's proj / fc2, M = 16 704) the 256-tile kernel is 8 - 17 %
+  // below 5/8 of the CUs.  At 77 % fill (198 tiles: the 224 x 224 ViT's proj / fc2, M = 16 704) the 256-tile kernel is 8 - 17 %
   // faster than 786 small tiles, at 39 % (100 tiles) the small tiles win by 28 % (profiles/r04_gemm_policy_224.txt)
-  return v >= 0 ? v : gemm_cu_count() * 5 / 8;
+  return gemm_cu_count() * 5 / 8;
 }
 }  // namespace unopose
 static int small_tiles_limit() { return unopose::gemm_small_tiles_limit(); }
@@ -70,13 +60,6 @@ static int small_tiles_limit() { return unopose::gemm_small_tiles_limit(); }
 // share one (a slot comes round again after 1024 launches: 20 forwards later).
 namespace unopose {
 int *gemm_sched_slot(hipStream_t stream) {
-#ifdef UNOPOSE_PROBE_BUILD  // `UNOPOSE_GEMM_DYN=0`: static tile lists (A/B, probe builds only)
-  static const bool on = [] {
-    const char *e = getenv("UNOPOSE_GEMM_DYN");
-    return !(e && *e == '0');
-  }();
-  if (!on) return nullptr;
-#endif
   // A launch being CAPTURED into a hipGraph gets static tile lists: a slot baked into a graph would be replayed while eager launches of
   // other streams cycle through the same ring (tickets shared between two running launches: tiles skipped or computed twice), and the
   // ring's first-use hipMalloc / hipMemset is not legal under capture.
@@ -98,41 +81,10 @@ int *gemm_sched_slot(hipStream_t stream) {
 }
 }  // namespace unopose
 
-// The four-wave, one-wave-per-SIMD kernel of round 5 (a generated, hand-placed instruction stream; it TIES this kernel on the ViT shapes:
-// profiles/r05_gemm4w_ablate.txt) lives under scripts/ubench/gemm4w/ with its generator and emulator; its variant builds
-// (scripts/ubench/gemm4w/g4w_var.py) compile this file with -DUNOPOSE_PROBE_GEMM4W to route the entry points to it.
-#ifdef UNOPOSE_PROBE_GEMM4W
-namespace unopose {
-bool gemm4w_ok(long M, int N, int K, int lda, int ldw, int ldc, int epilogue);
-int gemm4w_linear(const void *A, int lda, const void *W, int ldw, const float *bias, void *C, int ldc, long M, int N, int K, int epilogue, int nt,
-                  int *sched, hipStream_t s);
-}  // namespace unopose
-static int g_use_4w = 0;
-extern "C" int unopose_gemm4w_enable(int on) {
-  const int was = g_use_4w;
-  if (on >= 0) g_use_4w = on > 2 ? 2 : on;  // 0: off, 1: shapes with at least one tile per CU, 2: every shape the stream supports
-  return was;
-}
-#endif
-
 static int linear_bf16_dispatch(const void *A, int lda, const void *W, int ldw, const float *bias, void *C, int ldc, long M, int N, int K,
                                 int epilogue, hipStream_t s, const char *what) {
   const int tiles_n = N / GEMM_BN;
-#ifdef GEMM_PROBE_SKIP_TAIL  // timing probe (WRONG results): the tiles past the last whole round of the CUs are not computed -- what a perfect
-                             // split of the tail could gain in the pipelined step (scripts/build_variant.py notail -DGEMM_PROBE_SKIP_TAIL)
-  const int tiles_all = cdiv(M, GEMM_BM) * tiles_n, ncu_p = gemm_cu_count();
-  const int tiles = (tiles_all > ncu_p && tiles_all % ncu_p <= ncu_p / 8) ? tiles_all - tiles_all % ncu_p : tiles_all;
-#else
   const int tiles = cdiv(M, GEMM_BM) * tiles_n;
-#endif
-#ifdef UNOPOSE_PROBE_GEMM4W
-  if (g_use_4w == 2 && gemm4w_ok(M, N, K, lda, ldw, ldc, epilogue)) {  // (forced: small tile counts go through the stream as well)
-    if (int *const sched4 = gemm_sched_slot(s)) {
-      gemm4w_linear(A, lda, W, ldw, bias, C, ldc, M, N, K, epilogue, use_nt_store(M, N), sched4, s);
-      return check_launch(what);
-    }
-  }
-#endif
   if (tiles < small_tiles_limit()) return gemm_small_linear(A, W, bias, C, M, N, K, lda, ldw, ldc, epilogue, s);
   const int n_cu = gemm_cu_count();
   const int grid = tiles >= n_cu ? n_cu : ((tiles + 7) & ~7);
@@ -141,14 +93,6 @@ static int linear_bf16_dispatch(const void *A, int lda, const void *W, int ldw, 
   hipLaunchKernelGGL(gemm256_kernel<E>, dim3(grid), dim3(512), 0, s, (const u16 *)A, (const u16 *)W, bias, (u16 *)C, (int)M, N, K, tiles_n, \
                      tiles, nt, (const int *)nullptr, (const int *)nullptr, (const u16 *)nullptr, (const float *)nullptr,                     \
                      (const float *)nullptr, 0.f, lda, ldw, ldc, sched)
-#ifdef UNOPOSE_PROBE_GEMM4W
-  if (g_use_4w && tiles >= n_cu && gemm4w_ok(M, N, K, lda, ldw, ldc, epilogue)) {
-    if (int *const sched4 = gemm_sched_slot(s)) {
-      gemm4w_linear(A, lda, W, ldw, bias, C, ldc, M, N, K, epilogue, nt, sched4, s);
-      return check_launch(what);
-    }
-  }
-#endif
   int *const sched = tiles > grid ? gemm_sched_slot(s) : nullptr;  // (one tile per workgroup: nothing to schedule)
   if (epilogue == 1)
     UNOPOSE_LD_LAUNCH(1);

@@ -3,8 +3,6 @@
 // the same LDS image of an operand stage ([256 rows][128 B], 16-byte chunks XOR-swizzled by row on the SOURCE address of
 // the LDS-DMA) and the same persistent, lock-stepped tile walk.
 #pragma once
-#include <stdlib.h>
-
 #include "common.h"
 
 namespace unopose {
@@ -18,12 +16,8 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #define GEMM_ROWB 128                     // bytes of one operand row per stage (bf16: 64 k; fp32-class: 32 k as hi | lo)
 #define GEMM_OPBYTES (256 * GEMM_ROWB)    // one operand stage: 32 KiB
 #define GEMM_BUFBYTES (2 * GEMM_OPBYTES)  // A + W: 64 KiB
-#ifndef GEMM_GM
-#define GEMM_GM 1  // row panels per group of the tile order (1: row-major, the tiles sharing an A panel are neighbours in the sequence)
-#endif
-#ifndef GEMM_SKEW
-#define GEMM_SKEW 1  // tiles sharing a panel start 0..SKEW-1 K-tiles apart (1: together -- measured: least fabric traffic, same time)
-#endif
+constexpr int GEMM_GM = 1;    // row panels per group of the tile order (1: row-major, the tiles sharing an A panel are neighbours in the sequence)
+constexpr int GEMM_SKEW = 1;  // tiles sharing a panel start 0..SKEW-1 K-tiles apart (1: together -- measured: least fabric traffic, same time)
 
 // 0.5 x (1 + erf(x / sqrt 2)); erf(z) = 1 - (a1 t + ... + a5 t^5) exp(-z^2), t = 1 / (1 + p z), z >= 0
 // (Abramowitz-Stegun 7.1.26, |err| < 1.5e-7): the fp32-class epilogue.
@@ -81,7 +75,7 @@ int gemm_small_linear_ln(const void *A, const void *W, const float *bias, const 
                          void *C, long M, int K, hipStream_t s);
 
 int gemm_small_linear_f32(const void *As, const void *Ws, const float *bias, float *C, void *Cs, long M, int N, int K, int epilogue, hipStream_t s);
-// 256 x 256 tile counts below this run on the small-tile kernels (default: 5 / 8 of the CU count; UNOPOSE_GEMM_SMALL_TILES)
+// 256 x 256 tile counts below this run on the small-tile kernels (5 / 8 of the CU count)
 int gemm_small_tiles_limit();
 
 // A ticket slot for one launch of the persistent kernel with dynamic tile scheduling (gemm.hip), or nullptr (static tile lists).
@@ -96,10 +90,6 @@ inline int gemm_cu_count() {
     int cu = 0;
     if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu < 8) cu = 256;
     n_cu[dev] = cu & ~7;
-#ifdef UNOPOSE_PROBE_BUILD
-    const char *e = getenv("UNOPOSE_GEMM_CUS");  // probe: persistent grid capped below the CU count (leaves CUs to another stream)
-    if (e && *e && atoi(e) >= 8) n_cu[dev] = min(n_cu[dev], atoi(e) & ~7);
-#endif
   }
   return n_cu[dev];
 }

@@ -5,42 +5,12 @@
 
 namespace unopose {
 
-#ifndef GEMM_ABL
-#define GEMM_ABL 0  // scripts/ubench/gemm_var.py: 1 = no LDS-DMA in the K loop, 2 = no MFMAs, 3 = no fragment reads
-#endif
-#ifndef GEMM_EABL
-#define GEMM_EABL 0  // epilogue ablations: 1 = no global stores, 2 = no epilogue at all (accumulators kept live), 3 = no bias / activation math, 4 = EPI 5 without the loads of the old x
-#endif
-#ifndef GEMM_SAME
-#define GEMM_SAME 0  // probe: every tile streams the operands of tile (0, 0) -- an all-hit L2 stream under the full K loop
-#endif
-#ifndef GEMM_POLA
-#define GEMM_POLA 0  // cache policy of the A / W operand streams (gemm_dma16<POL>)
-#endif
-#ifndef GEMM_POLW
-#define GEMM_POLW 0
-#endif
-#ifndef GEMM_CW
-#define GEMM_CW -1  // column-blocked tile walk: column tiles per block (0: never; -1: chosen from the size of W, see the kernel)
-#endif
-#ifndef GEMM_PRIO
-#define GEMM_PRIO 0  // 1 = s_setprio 1 around the MFMA segment (measured: -1..2 % with 16-MFMA segments; scripts/ubench/gemm_r04_variants.hip)
-#endif
-#ifndef GEMM_LNF_ABL
-#define GEMM_LNF_ABL 0  // EPI 6 / 7 timing ablations (wrong results): 1 = no LayerNorm math in the epilogue, 2 = no c / row-partial DMA, 3 = both
-#endif
-#ifndef GEMM_XPOL
-#define GEMM_XPOL 2  // cache policy of EPI 5's accesses to the fp32 residual stream (aux bits; 2 = nt): a stream of 540 MB per launch that is next read a whole block later -- default policy: proj 209 us at M = 87 936, nt 178, nt + sc0 183, nt + sc1 184, sc1 195-207; fc2 439-442 with every policy (round 6)
-#endif
+// cache policy of EPI 5's accesses to the fp32 residual stream (aux bits; 2 = nt): a stream of 540 MB per launch that is next read a whole
+// block later -- default policy: proj 209 us at M = 87 936, nt 178, nt + sc0 183, nt + sc1 184, sc1 195-207; fc2 439-442 with every policy (round 6)
+constexpr int GEMM_XPOL = 2;
 #define GEMM_BK 64
-constexpr bool kMfma = GEMM_ABL != 2, kFrag = GEMM_ABL != 3, kDma = GEMM_ABL != 1;
-
-#ifndef GEMM_ROTX
-#define GEMM_ROTX 5  // K-tile rotation between XCDs (-1: spread evenly, xcd * nk / 8) and between steps
-#endif
-#ifndef GEMM_ROTS
-#define GEMM_ROTS 3
-#endif
+// K-tile rotation between XCDs (xcd * GEMM_ROTX) and between steps (step * GEMM_ROTS)
+constexpr int GEMM_ROTX = 5, GEMM_ROTS = 3;
 
 #define GEMM_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #define GEMM_WAIT_VM_(n) GEMM_WAIT_VM(n)
@@ -126,11 +96,8 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
   // Column-blocked walk: XCD x owns a contiguous range of ROW PANELS and walks it once per block of `cw` column tiles, so the
   // block's W panels stay in that XCD's 4 MiB L2 while its share of A streams through.  Used when W as a whole does not fit
   // (fc1: 4.7 MB; measured fabric reads 646 -> 417 MB per launch) and the row panels split evenly enough over the 8 XCDs.
-  int cw = GEMM_CW;
-  if (GEMM_CW < 0) {
-    cw = (size_t)N * K * ESZ > (size_t)(4u << 20) ? (2400 * 1024) / (GEMM_BN * K * ESZ) : 0;
-    if (cw < 3) cw = 0;
-  }
+  int cw = (size_t)N * K * ESZ > (size_t)(4u << 20) ? (2400 * 1024) / (GEMM_BN * K * ESZ) : 0;
+  if (cw < 3) cw = 0;
   const bool colwalk = cw > 0 && !GATHER && tiles_n > cw && ((tiles_m & 7) == 0 || tiles_m >= 512);
   const int rq = tiles_m >> 3, rr = tiles_m & 7;
   const int rows_x = rq + (xcd < rr ? 1 : 0), row_base = xcd < rr ? xcd * (rq + 1) : rr * (rq + 1) + (xcd - rr) * rq;
@@ -194,7 +161,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
     for (int j = 0; j < 4; ++j) {
       const int row = (wave >> 2) * 128 + (j >> 1) * 64 + (wave & 3) * 16 + (j & 1) * 8 + (lane >> 3);
       const int c = (lane & 7) ^ ((row >> 1) & 7);
-      int arow = (GEMM_SAME ? 0 : p.m0) + row;
+      int arow = p.m0 + row;
       if (GATHER) arow = max(row_list[p.m0 + row], 0);  // padding rows of a group (-1) compute on row 0; nobody reads them
       p.a_off[j] = (uint32_t)((size_t)arow * LDA * ESZ + c * 16);
     }
@@ -202,34 +169,33 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
     for (int i = 0; i < 2; ++i) {
       const int row = (wave >> 1) * 64 + (wave & 1) * 16 + i * 8 + (lane >> 3);
       const int c = (lane & 7) ^ ((row >> 1) & 7);
-      p.w_off[i] = (uint32_t)((size_t)((GEMM_SAME ? 0 : p.n0) + row) * LDW * ESZ + c * 16);
+      p.w_off[i] = (uint32_t)((size_t)(p.n0 + row) * LDW * ESZ + c * 16);
     }
     // K-tile rotation, uniform over the tiles an XCD runs together (they must stay on the same K-slice to share it) and
     // different between XCDs / steps: the chip as a whole touches different 128-byte columns at any instant.
     // GEMM_SKEW: tiles sharing a panel start 0..SKEW-1 K-tiles apart, so a K-slice one of them has fetched is RESIDENT in L2
     // when the others ask for it
-    const int skew = ((tm & 3) + tn) % (GEMM_SKEW > 1 ? GEMM_SKEW : 1);
-    p.rot = __builtin_amdgcn_readfirstlane(((GEMM_ROTX < 0 ? xcd * nk / 8 : xcd * GEMM_ROTX) + step * GEMM_ROTS + skew) % nk);
+    const int skew = ((tm & 3) + tn) % GEMM_SKEW;
+    p.rot = __builtin_amdgcn_readfirstlane((xcd * GEMM_ROTX + step * GEMM_ROTS + skew) % nk);
   };
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)smem;
   enum { H_A0 = 0, H_B0 = 1, H_B1 = 2, H_A1 = 3 };  // a K-tile's half-tiles in stream (= consumption) order
   // this wave's 2 pieces of half-tile `kind` of K-tile kt (rotation applied here) of tile p into the buffer at byte `bufoff`
   auto stage_half = [&](const TileP &p, int kind, int kt, uint32_t bufoff) {
-    if (!kDma) return;
     kt += __builtin_amdgcn_readfirstlane(p.rot);
     if (kt >= nk) kt -= nk;
     const int so = kt * GEMM_ROWB;
     if (kind == H_A0 || kind == H_A1) {
       const int ah = kind == H_A1 ? 1 : 0;
       const uint32_t la = lds0 + bufoff + a_dst + ah * 8192;
-      gemm_dma16<GEMM_POLA>(la, p.a_off[2 * ah], a_rs, so);
-      gemm_dma16<GEMM_POLA>(la + 1024, p.a_off[2 * ah + 1], a_rs, so);
+      gemm_dma16(la, p.a_off[2 * ah], a_rs, so);
+      gemm_dma16(la + 1024, p.a_off[2 * ah + 1], a_rs, so);
     } else {
       const int bh = kind == H_B1 ? 1 : 0;
       const uint32_t lw = lds0 + bufoff + w_dst + bh * 4096;
       const int sob = so + bh * (32 * ESZ) * LDW;
-      gemm_dma16<GEMM_POLW>(lw, p.w_off[0], w_rs, sob);
-      gemm_dma16<GEMM_POLW>(lw + 1024, p.w_off[1], w_rs, sob);
+      gemm_dma16(lw, p.w_off[0], w_rs, sob);
+      gemm_dma16(lw + 1024, p.w_off[1], w_rs, sob);
     }
   };
   // the tile's 256 bias values (1 KiB) by LDS-DMA as well: no ordinary load sits between the stream's counted waits.  Every wave
@@ -248,7 +214,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
     // have retired it: the 2 + 2 nparts pieces (d slice, c slice, row partials) are dealt over the waves, ONE per wave and slot (a wave
     // whose piece index is past the end repeats piece 0, so that every wave issues the same number of loads and the counted waits stay
     // uniform) instead of every wave fetching everything (+7 % on the L2 -> LDS stream of a K = 768 tile)
-    const int total = (GEMM_LNF_ABL & 2) ? 1 : 2 + 2 * nparts;
+    const int total = 2 + 2 * nparts;
 #pragma unroll
     for (int rep = 0; rep < (2 + 2 * GEMM_LNF_MAXPARTS + 7) / 8; ++rep) {
       if (rep * 8 >= total) break;  // (uniform)
@@ -321,7 +287,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
     for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const float4 bv = EPI == 3 || LNF || GEMM_EABL == 3 ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4 *>(bias_lds + wn * 64 + nb * 32 + 8 * g + 4 * hi);
+        const float4 bv = EPI == 3 || LNF ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4 *>(bias_lds + wn * 64 + nb * 32 + 8 * g + 4 * hi);
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb) {
           acc[nb][mb][4 * g + 0] = bv.x;
@@ -333,24 +299,17 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
 
     bf16x8 af[2][4], wf0[4], wf1[4];  // A half (2 row blocks x 4 k-substeps), B0, B1
     auto read_a = [&](const char *lb, int ah) {
-      if (!kFrag) return;
 #pragma unroll
       for (int mbl = 0; mbl < 2; ++mbl)
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) af[mbl][ks] = *reinterpret_cast<const bf16x8 *>(lb + a_base + ah * 8192 + mbl * 4096 + fr_off[ks]);
     };
     auto read_b = [&](const char *lb, int bh, bf16x8(&wf)[4]) {
-      if (!kFrag) return;
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) wf[ks] = *reinterpret_cast<const bf16x8 *>(lb + w_base + bh * 4096 + fr_off[ks]);
     };
     // one quadrant: 2 row blocks (ah) x 1 column block (bh) x 4 k-substeps, the two accumulators alternating
     auto mfma_q = [&](int ah, int bh, const bf16x8(&wf)[4]) {
-      if (!kMfma) {
-        asm volatile("" ::"v"(wf[0]), "v"(wf[1]), "v"(wf[2]), "v"(wf[3]), "v"(af[0][0]), "v"(af[0][1]), "v"(af[0][2]), "v"(af[0][3]), "v"(af[1][0]),
-                     "v"(af[1][1]), "v"(af[1][2]), "v"(af[1][3]));
-        return;
-      }
       if (F32) {
         // fragments 0 / 1 = the hi parts of the two 16-k blocks, 2 / 3 = their lo parts; small terms first
 #pragma unroll
@@ -384,9 +343,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      if (GEMM_PRIO) __builtin_amdgcn_s_setprio(1);
       compute();
-      if (GEMM_PRIO) __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
@@ -523,7 +480,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
           }
       }
     }
-    if constexpr (LNF && !(GEMM_LNF_ABL & 1)) {
+    if constexpr (LNF) {
       // ---- LayerNorm applied algebraically on the accumulators: out = rstd_r * acc - (rstd_r * mean_r) * c_n + d_n
       int l31 = l31_, hi = hi_;
       asm volatile("" : "+v"(l31), "+v"(hi));
@@ -581,10 +538,6 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
       auto load_round = [&](int r, f32x4(&dst)[4]) {  // round r = rows r * 16 .. + 15 of the wave's 128
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-          if (GEMM_EABL >= 4) {  // timing probes (wrong results): 4 = no loads of the old x (what an epilogue of stores alone costs); 5 = nor the fp32 store; 6 = nor the row sums; 7 = neither
-            dst[it] = f32x4{0.f, 0.f, 0.f, 0.f};
-            continue;
-          }
           dst[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x_rs, x_v0 + (uint32_t)(r * 16 + it * 4) * x_rowb, 0, GEMM_XPOL));
         }
       };
@@ -614,15 +567,13 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
           f32x4 v;
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = a[e] + o[e];
-          if (GEMM_EABL != 5 && GEMM_EABL != 7)
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), x_rs, x_v0 + (uint32_t)(r * 16 + it * 4) * x_rowb, 0, GEMM_XPOL);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), x_rs, x_v0 + (uint32_t)(r * 16 + it * 4) * x_rowb, 0, GEMM_XPOL);
           typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
           const u32x2 pk = {cvt_pk_bf16_f32(v[0], v[1]), cvt_pk_bf16_f32(v[2], v[3])};
           if (nt_store)
             __builtin_amdgcn_raw_buffer_store_b64(pk, c_rs, c_v0 + (uint32_t)(r * 16 + it * 4) * c_rowb, 0, 2);
           else
             __builtin_amdgcn_raw_buffer_store_b64(pk, c_rs, c_v0 + (uint32_t)(r * 16 + it * 4) * c_rowb, 0, 0);
-          if (GEMM_EABL == 6 || GEMM_EABL == 7) continue;
           float a1 = (v[0] + v[1]) + (v[2] + v[3]), a2 = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
           a1 += dpp_f32<0x111, 0xF>(a1, 0.f);  // row_shr 1, 2, 4, 8: the 16 lanes of a DPP row hold one matrix row; the sum lands in lane 15
           a2 += dpp_f32<0x111, 0xF>(a2, 0.f);
@@ -658,25 +609,19 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
     //      four passes of 32 rows per wave through a 4-KiB slot of the last K-tile's buffer (16-byte slots XOR-swizzled by
     //      row): waves 0-3 use the A1 half-tile slots, waves 4-7 the B1 slots -- the two the stream refills after the epilogue
     char *cw = smem + par + (wave < 4 ? 8192 + (wave & 1) * 4096 + (wave >> 1) * 16384 : GEMM_OPBYTES + 4096 + (wave - 4) * 8192);
-    if (GEMM_EABL == 2) {
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) asm volatile("" ::"v"(acc[nb][mb]));
-    }
     // stores go through a buffer descriptor: rows past M (ragged last tile) fall outside it and are dropped -- no branches
     const uint32_t c_v0 = GATHER ? (uint32_t)((((size_t)m0 + wm * 128 + (lane >> 3)) * GEMM_BN + wn * 64 + (lane & 7) * 8) * 2)
                                  : (uint32_t)((((size_t)m0 + wm * 128 + (lane >> 3)) * LDC + n0 + wn * 64 + (lane & 7) * 8) * 2);
     const uint32_t c_rowb = (uint32_t)((GATHER ? GEMM_BN : LDC) * 2);
 #pragma unroll
-    for (int mb = 0; mb < (GEMM_EABL == 2 ? 0 : 4); ++mb) {
+    for (int mb = 0; mb < 4; ++mb) {
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int nl = nb * 32 + 8 * g + 4 * hi;  // local column of the 4 values
           float v0 = acc[nb][mb][4 * g + 0], v1 = acc[nb][mb][4 * g + 1], v2 = acc[nb][mb][4 * g + 2], v3 = acc[nb][mb][4 * g + 3];
-          if ((EPI == 1 || EPI == 7) && GEMM_EABL != 3) {
+          if (EPI == 1 || EPI == 7) {
             v0 = gelu_bf16_class(v0);
             v1 = gelu_bf16_class(v1);
             v2 = gelu_bf16_class(v2);
@@ -704,9 +649,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const uint32_t off = c_v0 + (uint32_t)(mb * 32 + it * 8) * c_rowb;
-        if (GEMM_EABL == 1)
-          asm volatile("" ::"v"(cv[it]));
-        else if (nt_store)
+        if (nt_store)
           __builtin_amdgcn_raw_buffer_store_b128(cv[it], c_rs, off, 0, 2);  // aux 2 = nt
         else
           __builtin_amdgcn_raw_buffer_store_b128(cv[it], c_rs, off, 0, 0);

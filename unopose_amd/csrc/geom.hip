@@ -7,7 +7,6 @@
 //   * unopose_weighted_procrustes -- weighted_procrustes (utils/model_utils.py:667-743)
 // All 3x3 eigen / singular problems are solved by Jacobi rotations in registers
 // (jacobi3.h) instead of torch.svd.
-#include <cstdlib>
 
 #include "common.h"
 #include "jacobi3.h"
@@ -105,18 +104,6 @@ __global__ __launch_bounds__(256) void lrf_global_kernel(const float *__restrict
   }
 }
 
-#ifndef UNOPOSE_VOTE_VGPR
-#define UNOPOSE_VOTE_VGPR 0  // probes of the co-residency finding (scripts/ubench/geom_var.py)
-#endif
-#ifndef UNOPOSE_QLG_NOEIG
-#define UNOPOSE_QLG_NOEIG 0
-#endif
-#ifndef UNOPOSE_LRF_DEBUG
-#define UNOPOSE_LRF_DEBUG 0  // probe build (scripts/ubench): per-centre intermediates of the frame into a debug buffer
-#endif
-#if UNOPOSE_LRF_DEBUG
-__device__ float *g_lrf_dbg;
-#endif
 // -------------------------------------- fused ball_query + group + LRF ------
 // One wavefront per centre.  LDS: SoA copy of the cloud + one neighbour list per wave.
 // out (B,6,N,S): channels 0-2 = p_k - c (un-normalised), 3-5 = R^T (p_k - c) / radius
@@ -203,30 +190,8 @@ __global__ __launch_bounds__(256) void query_lrf_group_kernel(const float *__res
     a22 = wave_sum_f32(a22) * inv_s;
     Vec3 e0, e1, z0;
     float l0, l1, l2;
-#if UNOPOSE_QLG_NOEIG
-    {  // probe: no eigen-solver -- a direction computed with three multiplies and one rsqrt
-      const float nx = a00 + 1e-3f, ny = a01, nz = a02, rn = __builtin_amdgcn_rsqf(nx * nx + ny * ny + nz * nz);
-      z0 = v3(nx * rn, ny * rn, nz * rn);
-      e0 = e1 = z0;
-      l0 = l1 = l2 = 0.f;
-    }
-#else
     eig_sym3(a00, a01, a02, a11, a12, a22, e0, e1, z0, l0, l1, l2);
-#endif
 
-#if UNOPOSE_VOTE_VGPR
-    float votef = 0.f;  // probe: the sign vote as a wave sum of +-1 (exact in fp32), never through an SGPR mask
-    for (int l0i = 0; l0i < S; l0i += 64) {
-      const int l = l0i + lane;
-      float pr = 0.f;
-      if (l < S) {
-        const int k = nbr[l];
-        pr = z0.x * (cx - sx[k]) + z0.y * (cy - sy[k]) + z0.z * (cz - sz[k]);
-      }
-      votef += (pr > 1e-3f ? 1.f : 0.f) - (pr < -1e-3f ? 1.f : 0.f);
-    }
-    const int vote = (int)wave_sum_f32(votef);
-#else
     int vote = 0;
     for (int l0i = 0; l0i < S; l0i += 64) {
       const int l = l0i + lane;
@@ -237,7 +202,6 @@ __global__ __launch_bounds__(256) void query_lrf_group_kernel(const float *__res
       }
       vote += __builtin_popcountll(__ballot(pr > 1e-3f)) - __builtin_popcountll(__ballot(pr < -1e-3f));
     }
-#endif
     const Vec3 zp = vote < 0 ? scale(z0, -1.f) : z0;
 
     float vx = 0, vy = 0, vz = 0;
@@ -256,15 +220,6 @@ __global__ __launch_bounds__(256) void query_lrf_group_kernel(const float *__res
     vz = wave_sum_f32(vz);
     Vec3 xp, yp;
     finish_frame(zp, v3(vx, vy, vz), xp, yp);
-#if UNOPOSE_LRF_DEBUG
-    if (lane == 0 && g_lrf_dbg) {
-      float *d = g_lrf_dbg + ((size_t)b * N + j) * 24;
-      d[0] = a00; d[1] = a01; d[2] = a02; d[3] = a11; d[4] = a12; d[5] = a22;
-      d[6] = z0.x; d[7] = z0.y; d[8] = z0.z; d[9] = (float)vote; d[10] = vx; d[11] = vy; d[12] = vz;
-      d[13] = xp.x; d[14] = xp.y; d[15] = xp.z; d[16] = l0; d[17] = l1; d[18] = l2; d[19] = (float)cnt;
-      d[20] = e0.x; d[21] = e1.x; d[22] = cx; d[23] = inv_s;
-    }
-#endif
 
     float *row = O + (size_t)j * S;
     for (int l = lane; l < S; l += 64) {
@@ -483,25 +438,13 @@ int unopose_lrf_global(const float *pts, int B, int N, int use_ref_rad, float *o
   return check_launch("lrf_global");
 }
 
-#if UNOPOSE_LRF_DEBUG
-extern "C" int unopose_lrf_debug_buffer(float *buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_lrf_dbg), &buf, sizeof(buf)); }
-#endif
-
 int unopose_query_lrf_group(const float *xyz, int B, int N, float radius, int nsample, float *out,
                             unopose_stream_t stream) {
   UNOPOSE_REQUIRE(xyz && out, "query_lrf_group: null pointer");
   UNOPOSE_REQUIRE(B >= 0 && N >= 1 && nsample >= 1 && B <= 65535, "query_lrf_group: bad sizes");
   if (B == 0) return UNOPOSE_OK;
-  size_t lds = ((size_t)3 * N + 4 * (size_t)nsample) * 4;
+  const size_t lds = ((size_t)3 * N + 4 * (size_t)nsample) * 4;
   UNOPOSE_REQUIRE(lds <= 64 * 1024, "query_lrf_group: N=%d nsample=%d exceed the 64 KiB LDS tile", N, nsample);
-#ifdef UNOPOSE_QLG_LDS_PROBE_BUILD  // co-residency probe: compiled only into probe builds (scripts/build_variant.py -D...)
-  static const long lds_probe = getenv("UNOPOSE_QLG_LDS_PROBE") ? atol(getenv("UNOPOSE_QLG_LDS_PROBE")) : 0;
-  if (lds_probe > (long)lds) {
-    static bool opt[64];
-    if (lds_optin(opt, (const void *)query_lrf_group_kernel<false>, (size_t)lds_probe, "query_lrf_group") != UNOPOSE_OK) return UNOPOSE_ELAUNCH;
-    lds = (size_t)lds_probe;
-  }
-#endif
   const long centres = (long)B * N;
   int cpw = centres >= 65536 ? 8 : centres >= 16384 ? 4 : centres >= 4096 ? 2 : 1;
   dim3 grid(cdiv(N, 4 * cpw), B);

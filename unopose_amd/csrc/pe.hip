@@ -15,17 +15,9 @@
 #include "common.h"
 #include "jacobi3.h"
 
-#ifndef PE_SCAN_STEPS
-#define PE_SCAN_STEPS 4  // 64-candidate steps of the ball query per loop trip (A/B: scripts/build_variant.py -DPE_SCAN_STEPS=1)
-#endif
-#ifndef PE_GRID
-#define PE_GRID 1  // uniform grid for the bf16x3 kernel's ball query (A/B: -DPE_GRID=0 = the index-order scan over the whole cloud)
-#endif
-#ifndef PE_ABL
-#define PE_ABL 0  // timing probes (scripts/ubench/pe_ab.py; wrong results): 1 no MLP tiles, 2 no frame (eigen-solver, sign vote, x axis), 3 ball query over 64 points only, 4 no eigen-solver
-#endif
-
 namespace unopose {
+
+constexpr int PE_SCAN_STEPS = 4;  // 64-candidate steps of the ball query per loop trip (measured against 1 step per trip)
 
 typedef unsigned short u16;
 
@@ -61,7 +53,7 @@ __device__ __forceinline__ int pe_centre_frame(const float *sx, const float *sy,
                                                int ncand = -1, const PeGrid *grid = nullptr) {
   // ---- ball query (pointnet2 ball_query_gpu.cu:14-49 semantics)
   int cnt = 0, first = 0;
-  if (grid && ncand < 0 && PE_ABL != 3) {
+  if (grid && ncand < 0) {
     const int W = (N + 31) >> 5;
     for (int w = lane; w < W; w += 64) grid->bits[w] = 0u;
     // the nine runs: lane i < 9 looks up run (dy, dz) = (i % 3 - 1, i / 3 - 1)
@@ -117,7 +109,7 @@ __device__ __forceinline__ int pe_centre_frame(const float *sx, const float *sy,
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (cnt > 0) first = nbr[0];
   } else {
-  const int nscan = PE_ABL == 3 ? 64 : ncand >= 0 ? ncand : N;
+  const int nscan = ncand >= 0 ? ncand : N;
   int k0 = 0;
   // PE_SCAN_STEPS (four) 64-candidate steps per trip: their LDS reads, distance tests and ballots are independent, only the list positions chain
   // through cnt (one step at a time the loop was a chain of LDS -> VALU -> ballot -> scalar latencies: a third of a launch)
@@ -161,10 +153,6 @@ __device__ __forceinline__ int pe_centre_frame(const float *sx, const float *sy,
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-  if (PE_ABL == 2) {
-    xp = v3(1.f, 0.f, 0.f), yp = v3(0.f, 1.f, 0.f), zp = v3(0.f, 0.f, 1.f);
-    return cnt;
-  }
   // ---- local reference frame (LRF_batch, pointnet2_utils.py:436-481)
   // (measured and not kept, round 5: the three passes with the padding entries' terms as per-pass constants -- bit-identical, no faster:
   //  the frame's time is the eigen-solver and the wave reductions, not these reads)
@@ -179,10 +167,7 @@ __device__ __forceinline__ int pe_centre_frame(const float *sx, const float *sy,
   a11 = wave_sum_f32(a11) * inv_s; a12 = wave_sum_f32(a12) * inv_s; a22 = wave_sum_f32(a22) * inv_s;
   Vec3 e0, e1, z0;
   float l0, l1, l2;
-  if (PE_ABL == 4)  // (timing probe: no eigen-solver)
-    z0 = v3(a00 + 1e-3f, a01, a02), z0 = scale(z0, __builtin_amdgcn_rsqf(dot(z0, z0)));
-  else
-    eig_sym3(a00, a01, a02, a11, a12, a22, e0, e1, z0, l0, l1, l2);
+  eig_sym3(a00, a01, a02, a11, a12, a22, e0, e1, z0, l0, l1, l2);
   int vote = 0;
   for (int l0i = 0; l0i < S; l0i += 64) {
     const int l = l0i + lane;
@@ -421,15 +406,7 @@ __global__ __launch_bounds__(256) void pe_pack_weights_kernel(const float *__res
   if (tid < 128) L->b3[tid] = b3[tid];
 }
 
-#ifndef PE_WPE
-#define PE_WPE 0
-#endif
-#ifndef PE_PREFETCH
-#define PE_PREFETCH 1
-#endif
-#ifndef PE_NW
-#define PE_NW 4  // waves per workgroup of the bf16x3 kernel: two 4-wave workgroups per CU; 8 = one per CU (measured 4 % slower: -DPE_NW=8)
-#endif
+constexpr int PE_NW = 4;  // waves per workgroup of the bf16x3 kernel: two 4-wave workgroups per CU; 8 = one per CU (measured 4 % slower)
 __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3_kernel(
     const float *__restrict__ xyz, int N, float radius, int S, int cpw, const uint4 *__restrict__ image,
     const int *__restrict__ cand_in, const int *__restrict__ cand_cnt_in, int cand_stride, int *__restrict__ cand_out,
@@ -559,7 +536,7 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
       for (int r = 0; r < 16; ++r) rmax[t][r] = 0.f;  // post-ReLU values are >= 0
     // (tiles of nothing but copies of the first neighbour -- the padding of a list with fewer than S points inside the radius -- are
     //  skipped: their rows equal row 0's, the maximum cannot change; round 5)
-    const int S_eff = PE_ABL == 1 ? 0 : min(S, (max(min(cnt, S), 1) + 31) & ~31);  // (cnt == 0, a NaN centre: one tile of the all-point-0 list, like the reference)
+    const int S_eff = min(S, (max(min(cnt, S), 1) + 31) & ~31);  // (cnt == 0, a NaN centre: one tile of the all-point-0 list, like the reference)
     for (int t0 = 0; t0 < S_eff; t0 += 32) {
       // keep the weight fragments in LDS (re-read per tile) instead of letting the compiler hoist ~170
       // registers of loop-invariant operands: leaves room for 2 waves / SIMD so one wave's VALU phases
@@ -575,7 +552,6 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
       }
       bf16x8 xh, xl;
       pe_split8(f, xh, xl);
-#if PE_PREFETCH
       // The weight fragments and bias values of the NEXT group of MFMAs are read from LDS (into the other of two register sets) before
       // the current group is issued: left to the compiler every k-step's two fragments were read right in front of their three MFMAs
       // -- ~20 exposed LDS round trips per tile (round 4: the tile loop was latency-bound, the matrix pipe 36 % busy).
@@ -670,66 +646,6 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
 #pragma unroll
         for (int r = 0; r < 16; ++r) rmax[ot][r] = fmaxf(rmax[ot][r], h3[r]);
       }
-#else
-      // layer 1 (one k-step)
-      // (biases are folded into the accumulator initialisation: one move instead of move + add)
-      f32x16 h1;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) h1[r] = L->b1[cd_row(r, half)];
-      {
-        const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(&L->w1h[col][half * 8]);
-        const bf16x8 al = *reinterpret_cast<const bf16x8 *>(&L->w1l[col][half * 8]);
-        PE_MFMA3(h1, ah, al, xh, xl);
-      }
-      bf16x8 a1h[2], a1l[2];
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = fmaxf(h1[s2 * 8 + e], 0.f);
-        pe_split8(v, a1h[s2], a1l[s2]);
-      }
-      // layer 2: 32 -> 64
-      bf16x8 a2h[4], a2l[4];
-#pragma unroll
-      for (int ot = 0; ot < 2; ++ot) {
-        f32x16 h2;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) h2[r] = L->b2[ot * 32 + cd_row(r, half)];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(&L->w2h[ot * 32 + col][ks * 16 + half * 8]);
-          const bf16x8 al = *reinterpret_cast<const bf16x8 *>(&L->w2l[ot * 32 + col][ks * 16 + half * 8]);
-          PE_MFMA3(h2, ah, al, a1h[ks], a1l[ks]);
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          float v[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            v[e] = fmaxf(h2[s2 * 8 + e], 0.f);
-          pe_split8(v, a2h[ot * 2 + s2], a2l[ot * 2 + s2]);
-        }
-      }
-      // layer 3: 64 -> 128, running max
-#pragma unroll
-      for (int ot = 0; ot < 4; ++ot) {
-        f32x16 h3;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) h3[r] = L->b3[ot * 32 + cd_row(r, half)];
-        const int row = ot * 32 + col;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          const int kp = (ks * 16 + half * 8) ^ ((row & 7) << 3);
-          const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(&L->w3h[row][kp]);
-          const bf16x8 al = *reinterpret_cast<const bf16x8 *>(&L->w3l[row][kp]);
-          PE_MFMA3(h3, ah, al, a2h[ks], a2l[ks]);
-        }
-        // running max starts at 0, so max(rmax, h3) already includes the ReLU
-#pragma unroll
-        for (int r = 0; r < 16; ++r) rmax[ot][r] = fmaxf(rmax[ot][r], h3[r]);
-      }
-#endif
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -812,7 +728,7 @@ int unopose_pe_group_mlp_max_packed_out(const float *xyz, int B, int N, float ra
   size_t lds = sizeof(PeLdsB) + ((size_t)3 * N + PE_NW * 128) * 4 + (size_t)PE_NW * nsample * 2;
   UNOPOSE_REQUIRE(N < 65536 && lds <= 160 * 1024, "pe_group_mlp_max_packed: N=%d nsample=%d exceed the LDS tile", N, nsample);
   const size_t grid_bytes = ((size_t)PE_GCELLS + 2 + (size_t)N) * 2;
-  const int use_grid = PE_GRID && radius > 0.f && N <= 4096 && N >= 256 && lds + grid_bytes <= 160 * 1024 && (lds + grid_bytes <= 80 * 1024 || lds > 80 * 1024);
+  const int use_grid = radius > 0.f && N <= 4096 && N >= 256 && lds + grid_bytes <= 160 * 1024 && (lds + grid_bytes <= 80 * 1024 || lds > 80 * 1024);
   if (use_grid) lds += grid_bytes;
   lds = (lds + 15) & ~(size_t)15;
   static bool opt[64];

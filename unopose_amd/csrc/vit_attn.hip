@@ -13,7 +13,6 @@
 //   * O^T is transposed through 4 KiB of LDS so every token row is stored as 128 contiguous bytes.
 #include "common.h"
 #include "gemm_common.h"
-#include <cstdlib>
 
 namespace unopose {
 
@@ -57,16 +56,8 @@ constexpr int VA_BUF = VA_CHUNK * VA_LDK + 4 * VA_VSUB;  // u16 per chunk buffer
 // NW = wavefronts per workgroup: the K / V chunk staged in LDS is shared by NW * 32 QB queries, so a
 // larger workgroup amortises the staging (global loads, LDS writes, barriers: ~1/3 of the kernel at NW = 4
 // by ablation) over twice the MFMA work.
-// Ask the scheduler for an MFMA : VALU interleave in the pipelined tile (one matrix instruction, then up to VA_FILL
-// vector instructions, 16 times): the matrix pipe hides a few VALU issues per MFMA only if they sit in its shadow.
-#ifndef VA_FILL
-#define VA_FILL 6
-#endif
-#define VA_IL1 __builtin_amdgcn_sched_group_barrier(0x8, 1, 0); __builtin_amdgcn_sched_group_barrier(0x2, VA_FILL, 0);
-#define VA_INTERLEAVE VA_IL1 VA_IL1 VA_IL1 VA_IL1 VA_IL1 VA_IL1 VA_IL1 VA_IL1 VA_IL1 VA_IL1 VA_IL1 VA_IL1 VA_IL1 VA_IL1 VA_IL1 VA_IL1
-
-template <int QB, int NBUF, int NW, bool PIPE = false>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(QB == 1 ? 3 : (QB == 4 ? 1 : 2), QB == 1 ? 4 : (QB == 4 ? 1 : 2)))) void vit_attn_kernel(const u16 *__restrict__ qkv, int T, int H, int BH, int nq,
+template <int QB, int NBUF, int NW>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(QB == 1 ? 3 : 2, QB == 1 ? 4 : 2))) void vit_attn_kernel(const u16 *__restrict__ qkv, int T, int H, int BH, int nq,
                                                        float scale_log2e, u16 *__restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) u16 smem[];
   u16 (*Ot)[32][72] = reinterpret_cast<u16 (*)[32][72]>(smem);
@@ -240,33 +231,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(QB == 1
   auto chunk_compute = [&](int c0, const u16 *buf) {
     const int nk = min(VA_CHUNK, T - c0);  // valid keys of this chunk
     int kt = 0;
-    if (PIPE) {
-      // software pipeline over the chunk's full tiles: the K Q^T MFMAs of tile t+1 are issued BEFORE the softmax of tile t
-      // (two named score sets, static indexing), so the matrix pipe works under the exp / max / sum VALU stream
-      if (nk >= 32) {
-        f32x16 sa[QB], sb[QB];
-        qk_tile(buf, 0, sa);
-        for (;;) {
-          const bool more_b = kt + 64 <= nk;
-          if (more_b) qk_tile(buf, kt + 32, sb);
-          softmax_pv_tile(buf, kt, sa);
-          VA_INTERLEAVE
-          kt += 32;
-          if (!more_b) break;
-          const bool more_a = kt + 64 <= nk;
-          if (more_a) qk_tile(buf, kt + 32, sa);
-          softmax_pv_tile(buf, kt, sb);
-          VA_INTERLEAVE
-          kt += 32;
-          if (!more_a) break;
-        }
-      }
-    } else {
-      for (; kt + 32 <= nk; kt += 32) {  // full tiles: no masking, no branch between the MFMA groups
-        f32x16 s[QB];
-        qk_tile(buf, kt, s);
-        softmax_pv_tile(buf, kt, s);
-      }
+    for (; kt + 32 <= nk; kt += 32) {  // full tiles: no masking, no branch between the MFMA groups
+      f32x16 s[QB];
+      qk_tile(buf, kt, s);
+      softmax_pv_tile(buf, kt, s);
     }
     if (kt < nk) {  // the one partial tile of the sequence: keys >= T are masked out
       f32x16 s[QB];
@@ -347,7 +315,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(QB == 1
 //  * 4 waves per workgroup and TWO workgroups per CU (66.5 KiB of LDS each): with one 8-wave workgroup per CU the Q loads, the first
 //    chunk and the output pass of every workgroup ran with nothing else on the CU -- 9 workgroups per CU and launch, ~10 % of the time.
 // Same box, 64 x 12 x 1374: 489.6 us (vit_attn_kernel<2, 2, 8>) -> 472 (8 waves, LDS-DMA, 2 buffers) -> 450-469 us (this kernel);
-// a third chunk buffer (one workgroup per CU again): 622 us; results equal to the old kernel's (scripts/ubench/vit_attn_var.py).
+// a third chunk buffer (one workgroup per CU again): 622 us; results equal to the old kernel's.
 constexpr int VD_KBYTES = VA_CHUNK * 128;          // K chunk: [key][64 ch] bf16, swizzled
 constexpr int VD_VSUBB = 128 * 32 + 128;           // bytes per V sub-tile [128 keys][16 channels] + bank skew
 constexpr int VD_BUFB = VD_KBYTES + 4 * VD_VSUBB;  // 33 280 B per chunk buffer
@@ -560,15 +528,15 @@ static int launch_vit_attn_dma(const void *qkv, int B, int T, int H, void *out, 
   return check_launch("vit_attention");
 }
 
-template <int QB, int NBUF, int NW, bool PIPE = false>
+template <int QB, int NBUF, int NW>
 static int launch_vit_attn(const void *qkv, int B, int T, int H, void *out, hipStream_t stream) {
   static bool opt[64];  // > 64 KiB of LDS needs the opt-in, per device (idempotent; benign if raced)
   const size_t lds = (size_t)NBUF * VA_BUF * sizeof(u16);
-  if (lds_optin(opt, reinterpret_cast<const void *>(&vit_attn_kernel<QB, NBUF, NW, PIPE>), lds, "vit_attention") != UNOPOSE_OK) return UNOPOSE_ELAUNCH;
+  if (lds_optin(opt, reinterpret_cast<const void *>(&vit_attn_kernel<QB, NBUF, NW>), lds, "vit_attention") != UNOPOSE_OK) return UNOPOSE_ELAUNCH;
   const int BH = B * H, nq = cdiv(T, 32 * NW * QB);
   const float scale_log2e = 0.125f * 1.4426950408889634f;  // 1/sqrt(64) * log2(e)
   const long blocks = (long)cdiv(BH, 8) * nq * 8;
-  hipLaunchKernelGGL((vit_attn_kernel<QB, NBUF, NW, PIPE>), dim3((unsigned)blocks), dim3(NW * 64), lds, stream, (const u16 *)qkv, T,
+  hipLaunchKernelGGL((vit_attn_kernel<QB, NBUF, NW>), dim3((unsigned)blocks), dim3(NW * 64), lds, stream, (const u16 *)qkv, T,
                      H, BH, nq, scale_log2e, (u16 *)out);
   return check_launch("vit_attention");
 }
@@ -579,16 +547,6 @@ int unopose_vit_attention(const void *qkv, int B, int T, int H, void *out, unopo
   UNOPOSE_REQUIRE(qkv && out, "vit_attention: null pointer");
   UNOPOSE_REQUIRE(B >= 0 && T >= 1 && H >= 1 && (long)B * H * cdiv(T, 128) < (1L << 31), "vit_attention: bad sizes");
   if (B == 0) return UNOPOSE_OK;
-#ifdef UNOPOSE_PROBE_BUILD  // A/B routes exist in probe builds only (UNOPOSE_EXTRA_HIPCC_FLAGS=-DUNOPOSE_PROBE_BUILD; scripts/ubench/vit_attn_modes.py)
-  static const int nw_env = getenv("UNOPOSE_VIT_NW") ? atoi(getenv("UNOPOSE_VIT_NW")) : 8;
-  static const int qb4_env = getenv("UNOPOSE_VIT_QB4") ? atoi(getenv("UNOPOSE_VIT_QB4")) : 0;  // experiment: 1 wave / SIMD, 128 queries / wave
-  if (T >= 1024 && qb4_env == 1) return launch_vit_attn<4, 2, 4>(qkv, B, T, H, out, (hipStream_t)stream);
-  static const int dma_env = getenv("UNOPOSE_VIT_DMA") ? atoi(getenv("UNOPOSE_VIT_DMA")) : 1;  // 0: round 3's register-staged 8-wave kernel (A/B)
-  static const int pipe_env = getenv("UNOPOSE_VIT_PIPE") ? atoi(getenv("UNOPOSE_VIT_PIPE")) : 0;
-  if (T >= 1024 && dma_env != 1 && pipe_env == 1) return launch_vit_attn<2, 2, 8, true>(qkv, B, T, H, out, (hipStream_t)stream);
-  if (T >= 1024 && dma_env != 1 && nw_env != 8) return launch_vit_attn<2, 2, 4>(qkv, B, T, H, out, (hipStream_t)stream);
-  if (T >= 1024 && dma_env != 1) return launch_vit_attn<2, 2, 8>(qkv, B, T, H, out, (hipStream_t)stream);
-#endif
   // T >= 1024: LDS-DMA staging, 4-wave workgroups, two per CU; a qkv image past 2 GiB per crop (32-bit DMA offsets): the register-staged kernel
   if (T >= 1024 && (size_t)T * 3 * H * 64 * 2 < (1UL << 31)) return launch_vit_attn_dma(qkv, B, T, H, out, (hipStream_t)stream);
   if (T >= 1024) return launch_vit_attn<2, 2, 8>(qkv, B, T, H, out, (hipStream_t)stream);

@@ -19,25 +19,14 @@ namespace unopose {
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-#ifndef VS_CHUNK_KEYS
-#define VS_CHUNK_KEYS 128
-#endif
-constexpr int VS_CHUNK = VS_CHUNK_KEYS;  // keys staged per LDS chunk (128, or 64: half the LDS, two workgroups per CU)
+constexpr int VS_CHUNK = 128;  // keys staged per LDS chunk (128, or 64: half the LDS, two workgroups per CU)
 constexpr int VS_KPLANE = VS_CHUNK * 128;  // bytes of a K plane [key][64 channels] bf16; 16-byte chunk c of row r sits at c ^ ((r >> 1) & 7)
 constexpr int VS_VSUBB = VS_CHUNK * 32 + 128;   // bytes per V sub-tile [128 keys][16 channels] (+ bank skew), 4 per plane
 constexpr int VS_VPLANE = 4 * VS_VSUBB;
 constexpr int VS_VOFF = 2 * VS_KPLANE;     // K hi | K lo | V hi | V lo
 constexpr int VS_BUFB = 2 * VS_KPLANE + 2 * VS_VPLANE;  // 66560 B
 constexpr float VS_DEFER = 8.f;  // log2 of the largest P the deferred rescale lets through
-#ifndef VS_MODE
-#define VS_MODE 0  // 0: score MFMAs, softmax, P.V per tile; 1: the score MFMAs of tile t + 1 issued before the softmax of tile t (measured: slower at 3 waves / SIMD)
-#endif
-#ifndef VS_BATCH_READS
-#define VS_BATCH_READS 2  // 1: all fragments of a product read before its MFMAs; 2: the V fragments already before the softmax arithmetic (1101 -> 1086 -> 1079 us)
-#endif
-#ifndef VS_NW
-#define VS_NW 12   // wavefronts per workgroup = 3 per SIMD (154 VGPRs); 8: 1189 us, 12: 1086 us at 64 x 12 x 1374 (scripts/ubench/vit_attn_var.py)
-#endif
+constexpr int VS_NW = 12;  // wavefronts per workgroup = 3 per SIMD (154 VGPRs); 8: 1189 us, 12: 1086 us at 64 x 12 x 1374
 
 struct HLf {
   bf16x8 h, l;
@@ -128,7 +117,6 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
     // S^T = K Q^T: rows = 32 keys, cols = 32 queries
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#if VS_BATCH_READS
     // all eight K fragments first, then the twelve MFMAs (the compiler otherwise reads every k-step's pair right in front of its MFMAs:
     // four exposed LDS round trips instead of one)
     HLf kf[4];
@@ -141,14 +129,6 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) { VS_MFMA3(s, kf[ks], qf[ks]); }
-#else
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const char *kp = buf + kt * 128 + kfo[ks];
-      const HLf kf{*reinterpret_cast<const bf16x8 *>(kp), *reinterpret_cast<const bf16x8 *>(kp + VS_KPLANE)};
-      VS_MFMA3(s, kf, qf[ks]);
-    }
-#endif
     if (partial) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
@@ -156,8 +136,9 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
     }
   };
   auto softmax_pv_tile = [&](const char *buf, int kt, f32x16 &s) {
-#if VS_BATCH_READS == 2
-    HLf vfe[2][2];  // (experiment: the V fragments read before the softmax arithmetic)
+    // the tile's V fragments are read before the softmax arithmetic (measured: each read in front of its MFMAs 1101 us, all fragments of a
+    // product before its MFMAs 1086 us, the V fragments before the softmax 1079 us)
+    HLf vfe[2][2];
     {
       const char *vl0 = buf + vlane_off;
 #pragma unroll
@@ -174,7 +155,6 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
         }
       __builtin_amdgcn_sched_barrier(0);
     }
-#endif
     // online softmax with the deferred reference point (vit_attn.hip): per-lane select, no branch before the P.V MFMAs
     float mx = s[0];
 #pragma unroll
@@ -220,36 +200,14 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
       vl.h4[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + VS_VPLANE + 8 * 32));
       return HLf{vh.v, vl.v};
     };
-#if VS_BATCH_READS
-    HLf vfa[2][2];
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-#if VS_BATCH_READS == 2
-        vfa[s2][t] = vfe[s2][t];
-#else
-        vfa[s2][t] = v_frag(s2, t);
-#endif
-      }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const HLf pf{ph[s2].v, pl[s2].v};
-        VS_MFMA3(o[t], vfa[s2][t], pf);
+        VS_MFMA3(o[t], vfe[s2][t], pf);
       }
-#else
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const HLf vf = v_frag(s2, t);
-        const HLf pf{ph[s2].v, pl[s2].v};
-        VS_MFMA3(o[t], vf, pf);
-      }
-#endif
     if (__builtin_expect(__any(grow), 0)) {  // rare after the first tile: O = (O - D) alpha + D with D = this tile's P.V (vit_attn.hip)
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -270,23 +228,11 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
   auto chunk_compute = [&](int c0, const char *buf) {
     const int nk = min(VS_CHUNK, T - c0);
     const int nt = (nk + 31) >> 5;  // tiles of this chunk; only the sequence's last one can be partial
-    if (VS_MODE == 0) {
-      for (int t = 0; t < nt; ++t) {
-        f32x16 s;
-        qk_tile(buf, c0, t * 32, (t + 1) * 32 > nk, s);
-        softmax_pv_tile(buf, t * 32, s);
-      }
-    } else {
-      f32x16 sa, sb;
-      qk_tile(buf, c0, 0, 32 > nk, sa);
-      for (int t = 0; t < nt; t += 2) {
-        if (t + 1 < nt) qk_tile(buf, c0, (t + 1) * 32, (t + 2) * 32 > nk, sb);
-        softmax_pv_tile(buf, t * 32, sa);
-        if (t + 1 < nt) {
-          if (t + 2 < nt) qk_tile(buf, c0, (t + 2) * 32, (t + 3) * 32 > nk, sa);
-          softmax_pv_tile(buf, (t + 1) * 32, sb);
-        }
-      }
+    // (measured and not kept: the score MFMAs of tile t + 1 issued before the softmax of tile t -- slower at 3 waves / SIMD)
+    for (int t = 0; t < nt; ++t) {
+      f32x16 s;
+      qk_tile(buf, c0, t * 32, (t + 1) * 32 > nk, s);
+      softmax_pv_tile(buf, t * 32, s);
     }
   };
 
