@@ -1,6 +1,10 @@
 """bench.py -- (query,ref) pairs/s of UNOPose.forward on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--batch 32] [--img 518] [--dtype bf16|fp32]
+    python bench.py --gpus N --steps K --warmup W [--batch 32] [--img 518] [--dtype bf16|fp32] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` then runs the extra legs (rank 0
+of a 1-GPU run only, after the timed region) and adds them to the line: the fp32 leg, `ref_cached`, `contract_224`, `train`,
+the `roofline` / `roofline_other` kernel timings and the CPU baseline (each can be dropped with its `--no-*` option).
 
 A "step" is one UNOPose.forward over a batch of B synthetic (query,ref) pairs already resident in HBM
 (BASELINE configs[1]: batch 32, 2048 query points, 5000->2048 reference points, 518x518 crops; the
@@ -44,13 +48,16 @@ def parse(argv=None):
     ap.add_argument("--stages", default="auto", choices=["auto", "0", "1"],
                     help="PipelinedForward(stages=...): 1 = ViT half and matcher half of every forward on two streams, 0 = whole "
                          "forwards side by side, auto = by ViT size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the extra legs (fp32, ref_cached, contract_224, train, roofline, CPU baseline; "
+                         "about a minute more) and add them to the line.  Off: the line carries the headline measurement only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-all-cores", action="store_true",
-                    help="also time the CPU port once with EVERY hardware thread (adds ~10 min on a 256-thread host: 292 s per B=8 forward, "
-                         "0.027 pairs/s -- profiles/r03_bench_n1_bf16_s518_first_with_all_cores.json holds that run)")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-fp32", action="store_true", help="skip the extra fp32 (reference default precision) leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the bounded extra legs (`ref_cached`, `contract_224`, `train`)")
+                    help="with --full: also time the CPU port once with EVERY hardware thread (adds ~10 min on a 256-thread host: 292 s per "
+                         "B=8 forward, 0.027 pairs/s -- profiles/r03_bench_n1_bf16_s518_first_with_all_cores.json holds that run)")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline legs")
+    ap.add_argument("--no-fp32", action="store_true", help="with --full: skip the extra fp32 (reference default precision) leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the bounded extra legs (`ref_cached`, `contract_224`, `train`)")
     ap.add_argument("--train", action="store_true",
                     help="time the TRAINING step instead (BASELINE configs[3]: --batch 8 pairs per rank, --train-pts 4096 points per cloud, "
                          "224x224 crops, frozen backbone, Adam; N > 1: DistributedDataParallel, gradient all-reduce over RCCL).  A step = "
@@ -393,7 +400,7 @@ def _cpu_model_name():
 
 
 def cpu_baseline_leg(img, batches=(1, 4), timed=2, all_cores=False):
-    # (bounded to ~35 s of a default run: B = 1 gets one warm-up + `timed` forwards, the larger batch one warm-up + ONE timed forward --
+    # (bounded to ~35 s of a --full run: B = 1 gets one warm-up + `timed` forwards, the larger batch one warm-up + ONE timed forward --
     #  every number that can become `value` is a warmed one, first-touch allocations of a new batch size are not in it)
     """The oracle (torch-CPU port of the reference forward + the C `_ext` port; kind "port": the reference's
     Python cannot travel) timed on this host's cores on a bounded sample of the same workload
@@ -753,8 +760,9 @@ def main():
         return lambda: o
 
     log("model + batch ready (rank %d of %d)" % (rank, world))
-    for _ in range(args.warmup):
+    for i in range(args.warmup):
         out = step()
+        log("warm-up step %d of %d submitted" % (i + 1, args.warmup))  # no synchronisation: a slow first step shows as a late line
     if pipe is not None:
         pipe.drain()
     sync()
@@ -846,7 +854,7 @@ def main():
                                          "pairs_per_s_at_median": world * B / q(gaps, 0.5) * 1e3,
                                          "what": "(completion of step i + depth) - (completion of step i), / depth"}
         res["forward_latency_ms"] = {"median": q(lat, 0.5), "p10": q(lat, 0.1), "p90": q(lat, 0.9)}
-    if rank == 0 and world == 1 and not args.dry_run:
+    if args.full and rank == 0 and world == 1 and not args.dry_run:
         if amp and not args.no_fp32 and graphed is None:
             # the reference's default precision (configs/main_cfg.py:87-89: test.amp.enabled=False) through the same runner object as
             # `--dtype fp32` (PipelinedForward without autocast -- pipelined like the bf16 path since round 6: every fp32 GEMM is an own

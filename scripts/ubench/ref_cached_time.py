@@ -7,7 +7,7 @@ import unopose_amd.model.modules as mm
 if len(sys.argv) > 1:
     mm.SPARSE_SINGLE_CROP = sys.argv[1] == "True"
 flag = mm.SPARSE_SINGLE_CROP
-sys.argv = ["bench.py", "--no-cpu-baseline", "--no-fp32", "--no-roofline", "--steps", "5", "--warmup", "2"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-fp32", "--no-roofline", "--steps", "5", "--warmup", "2"]
 buf = io.StringIO()
 with redirect_stdout(buf):
     bench.main()

@@ -8,7 +8,7 @@ if len(sys.argv) > 2 and sys.argv[1] == "--one":
     import bench
     import unopose_amd.pipeline as pl
     pl.WHOLE_INTERNAL_OVERLAP = sys.argv[2] == "True"
-    sys.argv = ["bench.py", "--img", "224", "--no-cpu-baseline", "--no-roofline", "--steps", "40", "--warmup", "5"]
+    sys.argv = ["bench.py", "--img", "224", "--full", "--no-cpu-baseline", "--no-roofline", "--steps", "40", "--warmup", "5"]
     buf = io.StringIO()
     with redirect_stdout(buf):
         bench.main()

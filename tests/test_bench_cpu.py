@@ -57,3 +57,12 @@ def test_bench_dump_outputs_writes_the_last_step_and_repeats(tmp_path):
     assert runs[0]["pred_R"].shape == (4, 3, 3) and runs[0]["pred_R"].dtype == np.float32
     for k, v in runs[0].items():
         assert np.array_equal(v, runs[1][k]), k
+
+
+def test_bench_extra_legs_need_full():
+    """The extra legs (fp32, ref_cached, contract_224, train, roofline, CPU baseline) run only with `--full`; a plain run is the headline."""
+    import bench
+
+    assert not bench.parse(["--gpus", "1", "--steps", "2", "--warmup", "1"]).full
+    args = bench.parse(["--full", "--no-cpu-baseline"])
+    assert args.full and args.no_cpu_baseline and not args.no_roofline
