@@ -25,9 +25,6 @@
 
 namespace unopose {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-
 __device__ __forceinline__ u16 f2bf_rn(float f) {
   uint32_t u = __float_as_uint(f);
   u += 0x7FFFu + ((u >> 16) & 1u);

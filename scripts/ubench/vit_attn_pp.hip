@@ -24,8 +24,6 @@
 
 namespace unopose {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PP_CHUNK = 128;                      // keys per LDS chunk

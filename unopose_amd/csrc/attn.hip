@@ -14,15 +14,6 @@
 
 namespace unopose {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-
-__device__ __forceinline__ u16 f2bf_rn(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (u16)(u >> 16);
-}
-
 template <int XOR>
 __device__ __forceinline__ float swz_xor(float v) {  // butterfly step inside a 16-lane row, no LDS memory touched
   // (DPP rather than ds_swizzle through the LDS crossbar: DESIGN.md section 7)
@@ -178,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_kernel(const u16 *__restric
 #pragma unroll
   for (int t = 0; t < TA_NT; ++t)
 #pragma unroll
-    for (int h = 0; h < 4; ++h) Pl[wave][kg * 4 + h][t * 16 + li] = f2bf_rn(acc[t][h] * sm[h]);
+    for (int h = 0; h < 4; ++h) Pl[wave][kg * 4 + h][t * 16 + li] = f2bf(acc[t][h] * sm[h]);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -203,7 +194,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_kernel(const u16 *__restric
 #pragma unroll
     for (int ks = 0; ks < PK; ++ks) o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[ks], vb[nt & 1][ks], o, 0, 0, 0);
     // D row = (query row kg, head reg); channel tile nt belongs to head nt >> 2
-    if (kg < RW && n0 + kg < n) out[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = f2bf_rn(o[nt >> 2]);
+    if (kg < RW && n0 + kg < n) out[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = f2bf(o[nt >> 2]);
   }
 }
 
@@ -369,7 +360,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_rpe_dma_kernel(const u16 *_
 #pragma unroll
   for (int t = 0; t < TA_NT; ++t)
 #pragma unroll
-    for (int h = 0; h < 4; ++h) Pl[kg * 4 + h][t * 16 + li] = f2bf_rn(acc[t][h] * sm[h]);
+    for (int h = 0; h < 4; ++h) Pl[kg * 4 + h][t * 16 + li] = f2bf(acc[t][h] * sm[h]);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -391,7 +382,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_rpe_dma_kernel(const u16 *_
     f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < PK; ++ks) o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[ks], vb[nt & 1][ks], o, 0, 0, 0);
-    if (kg < rw_here) out[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = f2bf_rn(o[nt >> 2]);
+    if (kg < rw_here) out[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = f2bf(o[nt >> 2]);
   }
   // (the P staging above reused the ring: every lane's reads of it are done before the next tile's stream is started)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

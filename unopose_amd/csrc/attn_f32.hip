@@ -10,41 +10,15 @@
 
 namespace unopose {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ uint32_t af_cvt_pk(float a, float b) {
-  return cvt_pk_bf16_f32(a, b);
-}
-struct HL {
-  bf16x8 hi, lo;
-};
-__device__ __forceinline__ HL af_split(const float (&v)[8]) {
-  union { bf16x8 v; uint32_t w[4]; } H, L;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const uint32_t h = af_cvt_pk(v[2 * e], v[2 * e + 1]);
-    H.w[e] = h;
-    L.w[e] = af_cvt_pk(v[2 * e] - __uint_as_float(h << 16), v[2 * e + 1] - __uint_as_float(h & 0xFFFF0000u));
-  }
-  return HL{H.v, L.v};
-}
-__device__ __forceinline__ HL af_load8(const float *p) {  // 8 consecutive fp32 (32-byte aligned)
+__device__ __forceinline__ bf16x8_hl af_load8(const float *p) {  // 8 consecutive fp32 (32-byte aligned)
   const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
   const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  return af_split(v);
+  return split8_bf16(v);
 }
-__device__ __forceinline__ HL af_zero() {
+__device__ __forceinline__ bf16x8_hl af_zero() {
   float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  return af_split(z);
+  return split8_bf16(z);
 }
-#define AF_MFMA3_16(acc, A, B)                                              \
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A.hi, B.hi, acc, 0, 0, 0);  \
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A.hi, B.lo, acc, 0, 0, 0);  \
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A.lo, B.hi, acc, 0, 0, 0)
-#define AF_MFMA3_32(acc, A, B)                                              \
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.hi, B.hi, acc, 0, 0, 0);  \
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.hi, B.lo, acc, 0, 0, 0);  \
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.lo, B.hi, acc, 0, 0, 0)
 
 template <int XOR>
 __device__ __forceinline__ float af_swz(float v) {
@@ -84,7 +58,7 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
   auto ld8 = [](const float *p) { return Raw{*reinterpret_cast<const float4 *>(p), *reinterpret_cast<const float4 *>(p + 4)}; };
   auto sp8 = [](const Raw &r) {
     const float v[8] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w};
-    return af_split(v);
+    return split8_bf16(v);
   };
   constexpr int AF_PF = AF_PF_DEPTH, NPAIR = 8 * AF_NT;
   {
@@ -92,7 +66,7 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
     Raw ring[AF_PF];
 #pragma unroll
     for (int i = 0; i < AF_PF; ++i) ring[i] = ld8(addr(i));
-    HL a = af_zero();
+    bf16x8_hl a = af_zero();
 #pragma unroll
     for (int i = 0; i < NPAIR; ++i) {
       const int ks = i / AF_NT, t = i % AF_NT;
@@ -104,8 +78,8 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
       const Raw cur = ring[i % AF_PF];
       if (i + AF_PF < NPAIR) ring[i % AF_PF] = ld8(addr(i + AF_PF));
       if (t < nt_valid) {
-        const HL bv = sp8(cur);
-        AF_MFMA3_16(acc[t], a, bv);
+        const bf16x8_hl bv = sp8(cur);
+        acc[t] = mfma3_hh_hl_lh_16x16(a, bv, acc[t]);
       }
     }
   }
@@ -119,7 +93,7 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
 #pragma unroll
       for (int i = 0; i < AF_PF; ++i) ring[i] = ld8(addr(i));
       Raw araw = ld8(QP + kg * 8);  // the query-side fragment of k-step 0; the next one is fetched a whole k-step ahead
-      HL a = af_zero();
+      bf16x8_hl a = af_zero();
 #pragma unroll
       for (int i = 0; i < NPAIR; ++i) {
         const int ks = i / AF_NT, t = i % AF_NT;
@@ -131,8 +105,8 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
         const Raw cur = ring[i % AF_PF];
         if (i + AF_PF < NPAIR) ring[i % AF_PF] = ld8(addr(i + AF_PF));
         if (t < nt_valid) {
-          const HL bv = sp8(cur);
-          AF_MFMA3_16(acc[t], a, bv);
+          const bf16x8_hl bv = sp8(cur);
+          acc[t] = mfma3_hh_hl_lh_16x16(a, bv, acc[t]);
         }
       }
     }
@@ -178,7 +152,7 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  HL pa[AF_MP / 32];
+  bf16x8_hl pa[AF_MP / 32];
 #pragma unroll
   for (int ks = 0; ks < AF_MP / 32; ++ks) pa[ks] = af_load8(&Pl[wave][li][ks * 32 + kg * 8]);
   const float *VT = vt + (size_t)b * 256 * AF_MP;
@@ -195,8 +169,8 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
       if (ks == 0) o = f32x4{0.f, 0.f, 0.f, 0.f};
       const Raw cur = ring[i % AF_PF];
       if (i + AF_PF < NP2) ring[i % AF_PF] = ld8(addr(i + AF_PF));
-      const HL bv = sp8(cur);
-      AF_MFMA3_16(o, pa[ks], bv);
+      const bf16x8_hl bv = sp8(cur);
+      o = mfma3_hh_hl_lh_16x16(pa[ks], bv, o);
       if (ks == NKS - 1 && n0 + kg < n) out[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = o[nt >> 2];
     }
   }
@@ -206,7 +180,6 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
 // (the staging threads split every element once per workgroup; round 2 kept fp32 in LDS and every wave re-split every fragment at
 // every use -- ~190 of the ~340 vector instructions of a 32-key tile.  Same hi / lo values, so the results are bit-identical.)
 constexpr int AV_CHUNK = 64, AV_LDH = 64 + 8, AV_LDVH = AV_CHUNK + 8;  // u16 row strides of the K planes / the V^T planes
-typedef unsigned short u16f;
 
 // SPLIT: the output is written in the split layout of csrc/gemm_f32.hip (per token and 32-channel block one 128-byte line
 // [hi (32 bf16) | lo (32 bf16)]) -- the operand form of the projection GEMM that follows, instead of fp32 + a split pass.
@@ -215,8 +188,8 @@ __global__ __launch_bounds__(256) void vit_attn_f32_kernel(const float *__restri
                                                            float *__restrict__ out) {
   // K hi | K lo | V^T hi | V^T lo planes (4 x 9 KiB); the same memory is re-used as the output transpose buffer at the end
   constexpr int PLANE_K = AV_CHUNK * AV_LDH, PLANE_V = 64 * AV_LDVH;
-  __shared__ __attribute__((aligned(16))) u16f smem16[2 * PLANE_K + 2 * PLANE_V];
-  u16f *Kh = smem16, *Kl = smem16 + PLANE_K, *Vh = smem16 + 2 * PLANE_K, *Vl = Vh + PLANE_V;
+  __shared__ __attribute__((aligned(16))) u16 smem16[2 * PLANE_K + 2 * PLANE_V];
+  u16 *Kh = smem16, *Kl = smem16 + PLANE_K, *Vh = smem16 + 2 * PLANE_K, *Vl = Vh + PLANE_V;
   float (*Ot)[32][68] = reinterpret_cast<float (*)[32][68]>(smem16);
   static_assert(4 * 32 * 68 * 4 <= (2 * PLANE_K + 2 * PLANE_V) * 2, "output staging must fit the chunk buffers");
   const int b = blockIdx.z, h = blockIdx.y;
@@ -226,7 +199,7 @@ __global__ __launch_bounds__(256) void vit_attn_f32_kernel(const float *__restri
   const int col = lane & 31, hb = lane >> 5;
   const int C3 = 3 * H * 64;
   const float *base = qkv + (size_t)b * T * C3;
-  HL qf[4];
+  bf16x8_hl qf[4];
   {
     const float *qp = base + (size_t)min(q0 + col, T - 1) * C3 + h * 64 + hb * 8;
 #pragma unroll
@@ -249,23 +222,22 @@ __global__ __launch_bounds__(256) void vit_attn_f32_kernel(const float *__restri
       float4 vv = *reinterpret_cast<const float4 *>(src + 2 * H * 64);
       if (c0 + key >= T) vv = make_float4(0.f, 0.f, 0.f, 0.f);
       uint2 kh, kl;
-      kh.x = af_cvt_pk(kv.x, kv.y);
-      kh.y = af_cvt_pk(kv.z, kv.w);
-      kl.x = af_cvt_pk(kv.x - __uint_as_float(kh.x << 16), kv.y - __uint_as_float(kh.x & 0xFFFF0000u));
-      kl.y = af_cvt_pk(kv.z - __uint_as_float(kh.y << 16), kv.w - __uint_as_float(kh.y & 0xFFFF0000u));
+      kh.x = cvt_pk_bf16_f32(kv.x, kv.y);
+      kh.y = cvt_pk_bf16_f32(kv.z, kv.w);
+      kl.x = cvt_pk_bf16_lo(kv.x, kv.y, kh.x);
+      kl.y = cvt_pk_bf16_lo(kv.z, kv.w, kh.y);
       *reinterpret_cast<uint2 *>(Kh + key * AV_LDH + c4 * 4) = kh;
       *reinterpret_cast<uint2 *>(Kl + key * AV_LDH + c4 * 4) = kl;
-      const uint32_t vh0 = af_cvt_pk(vv.x, vv.y), vh1 = af_cvt_pk(vv.z, vv.w);
-      const uint32_t vl0 = af_cvt_pk(vv.x - __uint_as_float(vh0 << 16), vv.y - __uint_as_float(vh0 & 0xFFFF0000u));
-      const uint32_t vl1 = af_cvt_pk(vv.z - __uint_as_float(vh1 << 16), vv.w - __uint_as_float(vh1 & 0xFFFF0000u));
-      Vh[(c4 * 4 + 0) * AV_LDVH + key] = (u16f)(vh0 & 0xFFFF);
-      Vh[(c4 * 4 + 1) * AV_LDVH + key] = (u16f)(vh0 >> 16);
-      Vh[(c4 * 4 + 2) * AV_LDVH + key] = (u16f)(vh1 & 0xFFFF);
-      Vh[(c4 * 4 + 3) * AV_LDVH + key] = (u16f)(vh1 >> 16);
-      Vl[(c4 * 4 + 0) * AV_LDVH + key] = (u16f)(vl0 & 0xFFFF);
-      Vl[(c4 * 4 + 1) * AV_LDVH + key] = (u16f)(vl0 >> 16);
-      Vl[(c4 * 4 + 2) * AV_LDVH + key] = (u16f)(vl1 & 0xFFFF);
-      Vl[(c4 * 4 + 3) * AV_LDVH + key] = (u16f)(vl1 >> 16);
+      const uint32_t vh0 = cvt_pk_bf16_f32(vv.x, vv.y), vh1 = cvt_pk_bf16_f32(vv.z, vv.w);
+      const uint32_t vl0 = cvt_pk_bf16_lo(vv.x, vv.y, vh0), vl1 = cvt_pk_bf16_lo(vv.z, vv.w, vh1);
+      Vh[(c4 * 4 + 0) * AV_LDVH + key] = (u16)(vh0 & 0xFFFF);
+      Vh[(c4 * 4 + 1) * AV_LDVH + key] = (u16)(vh0 >> 16);
+      Vh[(c4 * 4 + 2) * AV_LDVH + key] = (u16)(vh1 & 0xFFFF);
+      Vh[(c4 * 4 + 3) * AV_LDVH + key] = (u16)(vh1 >> 16);
+      Vl[(c4 * 4 + 0) * AV_LDVH + key] = (u16)(vl0 & 0xFFFF);
+      Vl[(c4 * 4 + 1) * AV_LDVH + key] = (u16)(vl0 >> 16);
+      Vl[(c4 * 4 + 2) * AV_LDVH + key] = (u16)(vl1 & 0xFFFF);
+      Vl[(c4 * 4 + 3) * AV_LDVH + key] = (u16)(vl1 >> 16);
     }
     __syncthreads();
     if (!active) continue;
@@ -278,8 +250,8 @@ __global__ __launch_bounds__(256) void vit_attn_f32_kernel(const float *__restri
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         const int off = (kt + col) * AV_LDH + ks * 16 + hb * 8;
-        const HL kf{*reinterpret_cast<const bf16x8 *>(Kh + off), *reinterpret_cast<const bf16x8 *>(Kl + off)};
-        AF_MFMA3_32(s, kf, qf[ks]);
+        const bf16x8_hl kf{*reinterpret_cast<const bf16x8 *>(Kh + off), *reinterpret_cast<const bf16x8 *>(Kl + off)};
+        s = mfma3_hh_hl_lh_32x32(kf, qf[ks], s);
       }
       float mx = -3e38f;
 #pragma unroll
@@ -309,7 +281,7 @@ __global__ __launch_bounds__(256) void vit_attn_f32_kernel(const float *__restri
         float pv[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) pv[e] = s[s2 * 8 + e];
-        const HL pf = af_split(pv);
+        const bf16x8_hl pf = split8_bf16(pv);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           // keys kt + 16 s2 + 4 hb + {0..3} and + 8 + {0..3}: two 8-byte reads per plane
@@ -319,8 +291,8 @@ __global__ __launch_bounds__(256) void vit_attn_f32_kernel(const float *__restri
           VH.h2[1] = *reinterpret_cast<const uint2 *>(Vh + off + 8);
           VL.h2[0] = *reinterpret_cast<const uint2 *>(Vl + off);
           VL.h2[1] = *reinterpret_cast<const uint2 *>(Vl + off + 8);
-          const HL vf{VH.v, VL.v};
-          AF_MFMA3_32(o[t], vf, pf);
+          const bf16x8_hl vf{VH.v, VL.v};
+          o[t] = mfma3_hh_hl_lh_32x32(vf, pf, o[t]);
         }
       }
     }
@@ -346,8 +318,8 @@ __global__ __launch_bounds__(256) void vit_attn_f32_kernel(const float *__restri
         uint2 hi, lo;
         hi.x = cvt_pk_bf16_f32(v.x, v.y);
         hi.y = cvt_pk_bf16_f32(v.z, v.w);
-        lo.x = cvt_pk_bf16_f32(v.x - __uint_as_float(hi.x << 16), v.y - __uint_as_float(hi.x & 0xffff0000u));
-        lo.y = cvt_pk_bf16_f32(v.z - __uint_as_float(hi.y << 16), v.w - __uint_as_float(hi.y & 0xffff0000u));
+        lo.x = cvt_pk_bf16_lo(v.x, v.y, hi.x);
+        lo.y = cvt_pk_bf16_lo(v.z, v.w, hi.y);
         char *line = reinterpret_cast<char *>(out) + ((size_t)b * T + q0 + row) * (size_t)(H * 64) * 4 + (size_t)(c >> 5) * 128 + (c & 31) * 2;
         *reinterpret_cast<uint2 *>(line) = hi;
         *reinterpret_cast<uint2 *>(line + 64) = lo;

@@ -10,6 +10,8 @@ namespace unopose {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned short u16;
 
 // Last error text, readable through unopose_last_error().
 void set_error(const char *fmt, ...);
@@ -62,6 +64,54 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16_f32(float a, float b) {
   } r;
   r.h = __builtin_convertvector(v, unopose_bf16x2);
   return r.u;
+}
+
+// Scalar RNE fp32 -> bf16 in software.  Unlike the hardware conversion above it does not keep NaNs: 0x7FFFFFFF becomes -0.
+__device__ __forceinline__ u16 f2bf(float f) {
+  uint32_t u = __float_as_uint(f);
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return (u16)(u >> 16);
+}
+__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float(((uint32_t)h) << 16); }
+
+// ---- fp32-class operands on the bf16 matrix cores: x = hi + lo with hi = bf16(x), lo = bf16(x - hi) (x to 2^-17 relative),
+// and a product a b ~ ah bh + ah bl + al bh as three bf16 MFMAs with fp32 accumulation (the dropped al bl term is 2^-18 relative).
+// The lo pair of (a, b) whose packed hi pair is h = cvt_pk_bf16_f32(a, b).
+__device__ __forceinline__ uint32_t cvt_pk_bf16_lo(float a, float b, uint32_t h) {
+  return cvt_pk_bf16_f32(a - __uint_as_float(h << 16), b - __uint_as_float(h & 0xFFFF0000u));
+}
+struct bf16x8_hl {
+  bf16x8 hi, lo;
+};
+__device__ __forceinline__ bf16x8_hl split8_bf16(const float (&v)[8]) {
+  union {
+    bf16x8 v;
+    uint32_t w[4];
+  } H, L;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const uint32_t h = cvt_pk_bf16_f32(v[2 * e], v[2 * e + 1]);
+    H.w[e] = h;
+    L.w[e] = cvt_pk_bf16_lo(v[2 * e], v[2 * e + 1], h);
+  }
+  return bf16x8_hl{H.v, L.v};
+}
+// The three products, named by the order they are issued in (hh = a.hi b.hi, hl = a.hi b.lo, lh = a.lo b.hi).  The order
+// is part of the result: every kernel keeps the one it was validated with.
+__device__ __forceinline__ f32x4 mfma3_hh_hl_lh_16x16(bf16x8_hl a, bf16x8_hl b, f32x4 acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.hi, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.lo, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo, b.hi, acc, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma3_hh_hl_lh_32x32(bf16x8_hl a, bf16x8_hl b, f32x16 acc) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.hi, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.lo, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.lo, b.hi, acc, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma3_lh_hl_hh_32x32(bf16x8_hl a, bf16x8_hl b, f32x16 acc) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.lo, b.hi, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.lo, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.hi, acc, 0, 0, 0);
 }
 
 // ---- bilinear tap of a pixel of the (H, W) crop in the (hw, hw) feature map

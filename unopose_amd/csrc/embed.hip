@@ -18,20 +18,6 @@
 
 namespace unopose {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-
-__device__ __forceinline__ u16 f2bf(float f) {  // round-to-nearest-even
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (u16)(u >> 16);
-}
-__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float(((uint32_t)h) << 16); }
-// gfx950 packed fp32 -> bf16 conversion (RNE): low half = cvt(a), high half = cvt(b)
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
-  return cvt_pk_bf16_f32(a, b);
-}
-
 // sin and cos of |x| <~ 1e3 with ~1e-7 absolute error: 3-term Cody-Waite reduction by pi/2 + cephes
 // single-precision minimax polynomials on [-pi/4, pi/4].
 __device__ __forceinline__ void sincos_cw(float x, float &s, float &c) {
@@ -158,12 +144,11 @@ __global__ __launch_bounds__(GE_THREADS) void geo_embed_kernel(
     }
     // channel 2t = sin(w_t), 2t+1 = cos(w_t)  (transformer.py:278-282)
     const int rbase = c;  // = set * GE_PAIRS + row
-    const uint32_t p0 = cvt_pk_bf16(s0, c0), p1 = cvt_pk_bf16(s1, c1);
+    const uint32_t p0 = cvt_pk_bf16_f32(s0, c0), p1 = cvt_pk_bf16_f32(s1, c1);
     *reinterpret_cast<uint32_t *>(Ahi + ge_swz(rbase, lane * 4)) = p0;
     *reinterpret_cast<uint32_t *>(Ahi + ge_swz(rbase, (lane + 64) * 4)) = p1;
     if (SPLIT) {
-      const uint32_t q0 = cvt_pk_bf16(s0 - __uint_as_float(p0 << 16), c0 - __uint_as_float(p0 & 0xFFFF0000u));
-      const uint32_t q1 = cvt_pk_bf16(s1 - __uint_as_float(p1 << 16), c1 - __uint_as_float(p1 & 0xFFFF0000u));
+      const uint32_t q0 = cvt_pk_bf16_lo(s0, c0, p0), q1 = cvt_pk_bf16_lo(s1, c1, p1);
       *reinterpret_cast<uint32_t *>(Alo + ge_swz(rbase, lane * 4)) = q0;
       *reinterpret_cast<uint32_t *>(Alo + ge_swz(rbase, (lane + 64) * 4)) = q1;
     }
@@ -245,7 +230,7 @@ __global__ __launch_bounds__(GE_THREADS) void geo_embed_kernel(
       const float v = acc[0][r] + a + bsum;
       if (full || pair0 + 4 * khalf + row < nn) {
         if (OUT_BF16)
-          reinterpret_cast<u16 *>(out_)[obase + (size_t)row * GE_DIM] = (u16)cvt_pk_bf16(v, v);
+          reinterpret_cast<u16 *>(out_)[obase + (size_t)row * GE_DIM] = (u16)cvt_pk_bf16_f32(v, v);
         else
           reinterpret_cast<float *>(out_)[obase + (size_t)row * GE_DIM] = v;
       }
@@ -429,7 +414,7 @@ __global__ __launch_bounds__(1024) void geo_embed_table_kernel(const float *__re
         o[c] = v[0][c] + a + b4[c];
       }
       if (OUT_BF16)
-        *reinterpret_cast<uint2 *>(orow + (size_t)l * 512) = make_uint2(cvt_pk_bf16(o[0], o[1]), cvt_pk_bf16(o[2], o[3]));
+        *reinterpret_cast<uint2 *>(orow + (size_t)l * 512) = make_uint2(cvt_pk_bf16_f32(o[0], o[1]), cvt_pk_bf16_f32(o[2], o[3]));
       else
         *reinterpret_cast<gt_f4 *>(orow + (size_t)l * 1024) = gt_f4{o[0], o[1], o[2], o[3]};
       if (TRAIN && !MEAN) {

@@ -26,9 +26,6 @@
 
 namespace unopose {
 
-typedef __bf16 fa_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-
 constexpr int FA_D = 256;                 // feature width (out_proj)
 constexpr int FA_OWN = 256;               // owned indices per workgroup
 constexpr int FA_TILE = 32 * FA_D * 2;    // one swept tile: 16 KiB
@@ -97,9 +94,9 @@ __global__ __launch_bounds__(512) void fine_assign_kernel(const FAParams p) {
   const int i = 1 + blk * FA_OWN + wave * 32 + l31;
   const bool valid = i < NO;
   const int ic = valid ? i : NO - 1;
-  fa_bf16x8 bfr[16];
+  bf16x8 bfr[16];
 #pragma unroll
-  for (int ks = 0; ks < 16; ++ks) bfr[ks] = *reinterpret_cast<const fa_bf16x8 *>(own + (size_t)ic * FA_D + ks * 16 + hi * 8);
+  for (int ks = 0; ks < 16; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8 *>(own + (size_t)ic * FA_D + ks * 16 + hi * 8);
 
   // ---- per-index data of the swept side in LDS (modes 1, 2)
   float o_rs = 0.f, o_sc = 0.f;
@@ -156,7 +153,7 @@ __global__ __launch_bounds__(512) void fine_assign_kernel(const FAParams p) {
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) {
-      const fa_bf16x8 a = *reinterpret_cast<const fa_bf16x8 *>(tb + (ks >> 2) * 4096 + fr[ks & 3]);
+      const bf16x8 a = *reinterpret_cast<const bf16x8 *>(tb + (ks >> 2) * 4096 + fr[ks & 3]);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bfr[ks], acc, 0, 0, 0);
     }
     // acc[4 q + e] = x(owned index of this lane, swept index 32 t + 8 q + 4 hi + e)

@@ -9,17 +9,9 @@
 
 namespace unopose {
 
-typedef unsigned short u16;
-__device__ __forceinline__ u16 fu_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (u16)(u >> 16);
-}
-__device__ __forceinline__ float fu_bf2f(u16 h) { return __uint_as_float(((uint32_t)h) << 16); }
-
 template <bool IN_BF16>
 __device__ __forceinline__ float fu_load(const void *p, size_t i) {
-  return IN_BF16 ? fu_bf2f(reinterpret_cast<const u16 *>(p)[i]) : reinterpret_cast<const float *>(p)[i];
+  return IN_BF16 ? bf2f(reinterpret_cast<const u16 *>(p)[i]) : reinterpret_cast<const float *>(p)[i];
 }
 
 // out[r,:] = LayerNorm(a[r,:] (+ b[r,:])) * w + bias ; one wavefront per row, C <= 64 * 16
@@ -59,7 +51,7 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const void *__restri
     if (c < C) {
       const float y = (v[i] - mean) * rstd * w[c] + bias[c];
       if (OUT_BF16)
-        reinterpret_cast<u16 *>(out)[(size_t)r * ldo + c] = fu_f2bf(y);
+        reinterpret_cast<u16 *>(out)[(size_t)r * ldo + c] = f2bf(y);
       else
         reinterpret_cast<float *>(out)[(size_t)r * ldo + c] = y;
     }
@@ -72,7 +64,7 @@ template <bool BF>
 __device__ __forceinline__ float4 fu_load4(const void *p, size_t i) {
   if (BF) {
     const uint2 r = *reinterpret_cast<const uint2 *>(reinterpret_cast<const u16 *>(p) + i);
-    return make_float4(fu_bf2f((u16)(r.x & 0xFFFF)), fu_bf2f((u16)(r.x >> 16)), fu_bf2f((u16)(r.y & 0xFFFF)), fu_bf2f((u16)(r.y >> 16)));
+    return make_float4(bf2f((u16)(r.x & 0xFFFF)), bf2f((u16)(r.x >> 16)), bf2f((u16)(r.y & 0xFFFF)), bf2f((u16)(r.y >> 16)));
   }
   return *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(p) + i);
 }
@@ -121,8 +113,8 @@ __global__ __launch_bounds__(256) void add_layernorm_vec4_kernel(const void *__r
       const float y2 = (v[i].z - mean) * rstd * wv.z + bv.z, y3 = (v[i].w - mean) * rstd * wv.w + bv.w;
       if (OUT_BF16) {
         uint2 o;
-        o.x = (uint32_t)fu_f2bf(y0) | ((uint32_t)fu_f2bf(y1) << 16);
-        o.y = (uint32_t)fu_f2bf(y2) | ((uint32_t)fu_f2bf(y3) << 16);
+        o.x = (uint32_t)f2bf(y0) | ((uint32_t)f2bf(y1) << 16);
+        o.y = (uint32_t)f2bf(y2) | ((uint32_t)f2bf(y3) << 16);
         *reinterpret_cast<uint2 *>(reinterpret_cast<u16 *>(out) + (size_t)r * ldo + c) = o;
       } else {
         *reinterpret_cast<float4 *>(reinterpret_cast<float *>(out) + (size_t)r * ldo + c) = make_float4(y0, y1, y2, y3);
@@ -152,10 +144,10 @@ __global__ __launch_bounds__(256) void scale_residual_layernorm_kernel(float *__
       xv = *reinterpret_cast<const float4 *>(x + (size_t)r * C + c);
       const uint2 yv = *reinterpret_cast<const uint2 *>(y + (size_t)r * C + c);
       const float4 g = *reinterpret_cast<const float4 *>(gamma + c);
-      xv.x += g.x * fu_bf2f((u16)(yv.x & 0xFFFF));
-      xv.y += g.y * fu_bf2f((u16)(yv.x >> 16));
-      xv.z += g.z * fu_bf2f((u16)(yv.y & 0xFFFF));
-      xv.w += g.w * fu_bf2f((u16)(yv.y >> 16));
+      xv.x += g.x * bf2f((u16)(yv.x & 0xFFFF));
+      xv.y += g.y * bf2f((u16)(yv.x >> 16));
+      xv.z += g.z * bf2f((u16)(yv.y & 0xFFFF));
+      xv.w += g.w * bf2f((u16)(yv.y >> 16));
       *reinterpret_cast<float4 *>(x + (size_t)r * C + c) = xv;
     }
     v[i * 4 + 0] = xv.x; v[i * 4 + 1] = xv.y; v[i * 4 + 2] = xv.z; v[i * 4 + 3] = xv.w;
@@ -181,10 +173,10 @@ __global__ __launch_bounds__(256) void scale_residual_layernorm_kernel(float *__
     if (c < C) {
       const float4 wv = *reinterpret_cast<const float4 *>(w + c), bv = *reinterpret_cast<const float4 *>(bias + c);
       uint2 o;
-      o.x = (uint32_t)fu_f2bf((v[i * 4 + 0] - mean) * rstd * wv.x + bv.x) |
-            ((uint32_t)fu_f2bf((v[i * 4 + 1] - mean) * rstd * wv.y + bv.y) << 16);
-      o.y = (uint32_t)fu_f2bf((v[i * 4 + 2] - mean) * rstd * wv.z + bv.z) |
-            ((uint32_t)fu_f2bf((v[i * 4 + 3] - mean) * rstd * wv.w + bv.w) << 16);
+      o.x = (uint32_t)f2bf((v[i * 4 + 0] - mean) * rstd * wv.x + bv.x) |
+            ((uint32_t)f2bf((v[i * 4 + 1] - mean) * rstd * wv.y + bv.y) << 16);
+      o.y = (uint32_t)f2bf((v[i * 4 + 2] - mean) * rstd * wv.z + bv.z) |
+            ((uint32_t)f2bf((v[i * 4 + 3] - mean) * rstd * wv.w + bv.w) << 16);
       *reinterpret_cast<uint2 *>(out + (size_t)r * C + c) = o;
     }
   }
@@ -244,8 +236,8 @@ __global__ __launch_bounds__(256) void scale_residual_layernorm_f32_kernel(float
       uint2 h, l;
       h.x = cvt_pk_bf16_f32(n0, n1);
       h.y = cvt_pk_bf16_f32(n2, n3);
-      l.x = cvt_pk_bf16_f32(n0 - __uint_as_float(h.x << 16), n1 - __uint_as_float(h.x & 0xffff0000u));
-      l.y = cvt_pk_bf16_f32(n2 - __uint_as_float(h.y << 16), n3 - __uint_as_float(h.y & 0xffff0000u));
+      l.x = cvt_pk_bf16_lo(n0, n1, h.x);
+      l.y = cvt_pk_bf16_lo(n2, n3, h.y);
       // channels c .. c+3 = half of the 8-element chunk c / 8 of 32-channel block c / 32: hi at +0, lo at +64 of the 128-byte line
       char *line = out + (size_t)r * out_ld + (size_t)(c >> 5) * 128 + ((c >> 3) & 3) * 16 + ((c >> 2) & 1) * 8;
       *reinterpret_cast<uint2 *>(line) = h;
@@ -262,10 +254,10 @@ __global__ __launch_bounds__(256) void scale_residual_kernel(float *__restrict__
     const uint2 yv = reinterpret_cast<const uint2 *>(y)[i];
     const int c = (int)((i * 4) % C);
     const float4 g = *reinterpret_cast<const float4 *>(gamma + c);
-    xv.x += g.x * fu_bf2f((u16)(yv.x & 0xFFFF));
-    xv.y += g.y * fu_bf2f((u16)(yv.x >> 16));
-    xv.z += g.z * fu_bf2f((u16)(yv.y & 0xFFFF));
-    xv.w += g.w * fu_bf2f((u16)(yv.y >> 16));
+    xv.x += g.x * bf2f((u16)(yv.x & 0xFFFF));
+    xv.y += g.y * bf2f((u16)(yv.x >> 16));
+    xv.z += g.z * bf2f((u16)(yv.y & 0xFFFF));
+    xv.w += g.w * bf2f((u16)(yv.y >> 16));
     reinterpret_cast<float4 *>(x)[i] = xv;
   }
 }
@@ -299,8 +291,8 @@ __global__ __launch_bounds__(256) void bilinear_sample_kernel(const void *__rest
   for (int k = 0; k < 4; ++k) {
     if (IN_BF16) {
       const uint2 r = *reinterpret_cast<const uint2 *>(reinterpret_cast<const u16 *>(z) + offs[k] + lane * 4);
-      v[k][0] = fu_bf2f((u16)(r.x & 0xFFFF)); v[k][1] = fu_bf2f((u16)(r.x >> 16));
-      v[k][2] = fu_bf2f((u16)(r.y & 0xFFFF)); v[k][3] = fu_bf2f((u16)(r.y >> 16));
+      v[k][0] = bf2f((u16)(r.x & 0xFFFF)); v[k][1] = bf2f((u16)(r.x >> 16));
+      v[k][2] = bf2f((u16)(r.y & 0xFFFF)); v[k][3] = bf2f((u16)(r.y >> 16));
     } else {
       const float4 r = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(z) + offs[k] + lane * 4);
       v[k][0] = r.x; v[k][1] = r.y; v[k][2] = r.z; v[k][3] = r.w;

@@ -27,17 +27,11 @@ __global__ __launch_bounds__(256) void split_bf16x2_kernel(const float *__restri
   const int c = (int)(i - r * k8);  // 8-element chunk of the row
   const float4 a = *reinterpret_cast<const float4 *>(X + r * K + c * 8), b = *reinterpret_cast<const float4 *>(X + r * K + c * 8 + 4);
   const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    h[j] = cvt_pk_bf16_f32(v[2 * j], v[2 * j + 1]);
-    const float r0 = v[2 * j] - __uint_as_float(h[j] << 16), r1 = v[2 * j + 1] - __uint_as_float(h[j] & 0xffff0000u);
-    l[j] = cvt_pk_bf16_f32(r0, r1);
-  }
+  const bf16x8_hl s = split8_bf16(v);
   // k-block j = c / 4 (32 k), chunk c % 4 inside the block; hi at +0, lo at +64 bytes of the 128-byte line
   char *line = reinterpret_cast<char *>(Xs) + (size_t)r * K * 4 + (size_t)(c >> 2) * 128 + (c & 3) * 16;
-  *reinterpret_cast<uint4 *>(line) = make_uint4(h[0], h[1], h[2], h[3]);
-  *reinterpret_cast<uint4 *>(line + 64) = make_uint4(l[0], l[1], l[2], l[3]);
+  *reinterpret_cast<bf16x8 *>(line) = s.hi;
+  *reinterpret_cast<bf16x8 *>(line + 64) = s.lo;
 }
 
 }  // namespace unopose

@@ -369,25 +369,22 @@ __global__ __launch_bounds__(256, 2) void gemm_small_f32_kernel(const char *__re
     const char *lb = smem + buf * STAGE;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 wh[2], wl[2], ah[2], al[2];
+      bf16x8_hl w[2], a[2];
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
-        wh[nb] = *reinterpret_cast<const bf16x8 *>(lb + w_base + nb * 4096 + fr_off[ks]);
-        wl[nb] = *reinterpret_cast<const bf16x8 *>(lb + w_base + nb * 4096 + fr_off[2 + ks]);
+        w[nb].hi = *reinterpret_cast<const bf16x8 *>(lb + w_base + nb * 4096 + fr_off[ks]);
+        w[nb].lo = *reinterpret_cast<const bf16x8 *>(lb + w_base + nb * 4096 + fr_off[2 + ks]);
       }
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb) {
-        ah[mb] = *reinterpret_cast<const bf16x8 *>(lb + a_base + mb * 4096 + fr_off[ks]);
-        al[mb] = *reinterpret_cast<const bf16x8 *>(lb + a_base + mb * 4096 + fr_off[2 + ks]);
+        a[mb].hi = *reinterpret_cast<const bf16x8 *>(lb + a_base + mb * 4096 + fr_off[ks]);
+        a[mb].lo = *reinterpret_cast<const bf16x8 *>(lb + a_base + mb * 4096 + fr_off[2 + ks]);
       }
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {  // (the order of gemm_kernel.h's F32 form: small terms first)
-          acc[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[nb], ah[mb], acc[nb][mb], 0, 0, 0);
-          acc[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[nb], al[mb], acc[nb][mb], 0, 0, 0);
-          acc[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[nb], ah[mb], acc[nb][mb], 0, 0, 0);
-        }
+        for (int mb = 0; mb < 2; ++mb)  // (the order of gemm_kernel.h's F32 form: small terms first)
+          acc[nb][mb] = mfma3_lh_hl_hh_32x32(w[nb], a[mb], acc[nb][mb]);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -433,8 +430,8 @@ __global__ __launch_bounds__(256, 2) void gemm_small_f32_kernel(const char *__re
         uint2 h, l;
         h.x = cvt_pk_bf16_f32(v.x, v.y);
         h.y = cvt_pk_bf16_f32(v.z, v.w);
-        l.x = cvt_pk_bf16_f32(v.x - __uint_as_float(h.x << 16), v.y - __uint_as_float(h.x & 0xffff0000u));
-        l.y = cvt_pk_bf16_f32(v.z - __uint_as_float(h.y << 16), v.w - __uint_as_float(h.y & 0xffff0000u));
+        l.x = cvt_pk_bf16_lo(v.x, v.y, h.x);
+        l.y = cvt_pk_bf16_lo(v.z, v.w, h.y);
         char *line = Cs + (size_t)m * N * 4 + (size_t)(n >> 5) * 128 + (n & 31) * 2;
         *reinterpret_cast<uint2 *>(line) = h;
         *reinterpret_cast<uint2 *>(line + 64) = l;

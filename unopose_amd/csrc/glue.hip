@@ -13,8 +13,6 @@
 
 namespace unopose {
 
-typedef unsigned short u16;
-
 // ---- (B,3,S,S) fp32 x 2 -> (2 B P, Kp) bf16, P = (S/14)^2, column = c * 196 + py * 14 + px, columns >= 588 zero.
 // One workgroup per (crop, patch row gy): the 3 x 14 x S strip is read with coalesced rows and written patch-major.
 //      SPLIT: the fp32 values in the split layout of csrc/gemm_f32.hip instead (per row and 32-column block one 128-byte line [hi (32 bf16) |
@@ -44,7 +42,7 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float *__restrict__
     }
     if (SPLIT) {
       const uint32_t hi = cvt_pk_bf16_f32(v[0], v[1]);
-      const uint32_t lo = cvt_pk_bf16_f32(v[0] - __uint_as_float(hi << 16), v[1] - __uint_as_float(hi & 0xffff0000u));
+      const uint32_t lo = cvt_pk_bf16_lo(v[0], v[1], hi);
       u16 *line = dst + (size_t)gx * Kp * 2 + (size_t)(k2 >> 5) * 64 + (k2 & 31);  // (u16 units: 64 per 128-byte line, hi half first)
       *reinterpret_cast<uint32_t *>(line) = hi;
       *reinterpret_cast<uint32_t *>(line + 32) = lo;
@@ -116,8 +114,8 @@ __global__ __launch_bounds__(256) void vit_tokens_layernorm_kernel(const void *_
       uint2 h, l;
       h.x = cvt_pk_bf16_f32(y0, y1);
       h.y = cvt_pk_bf16_f32(y2, y3);
-      l.x = cvt_pk_bf16_f32(y0 - __uint_as_float(h.x << 16), y1 - __uint_as_float(h.x & 0xffff0000u));
-      l.y = cvt_pk_bf16_f32(y2 - __uint_as_float(h.y << 16), y3 - __uint_as_float(h.y & 0xffff0000u));
+      l.x = cvt_pk_bf16_lo(y0, y1, h.x);
+      l.y = cvt_pk_bf16_lo(y2, y3, h.y);
       char *line = reinterpret_cast<char *>(n1) + (size_t)r * C * 4 + (size_t)(c >> 5) * 128 + ((c >> 3) & 3) * 16 + ((c >> 2) & 1) * 8;
       *reinterpret_cast<uint2 *>(line) = h;
       *reinterpret_cast<uint2 *>(line + 64) = l;
@@ -391,13 +389,13 @@ __global__ __launch_bounds__(256) void rigid_rows_bf16_kernel(const float *__res
                                                               u16 *__restrict__ out) {
   const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
-  auto f2bf_rn = [](float v) { return (u16)(cvt_pk_bf16_f32(v, 0.f) & 0xffffu); };
-  auto rb = [&](float v) { return __uint_as_float((uint32_t)f2bf_rn(v) << 16); };
+  auto f2bf_hw = [](float v) { return (u16)(cvt_pk_bf16_f32(v, 0.f) & 0xffffu); };
+  auto rb = [&](float v) { return __uint_as_float((uint32_t)f2bf_hw(v) << 16); };
   const float *pp = p + ((size_t)b * N + i) * 3, *tt = t + b * 3, *Rb = R + b * 9;
   const float x0 = rb(pp[0] - tt[0]), x1 = rb(pp[1] - tt[1]), x2 = rb(pp[2] - tt[2]);
   u16 *o = out + ((size_t)b * N + i) * 3;
 #pragma unroll
-  for (int j = 0; j < 3; ++j) o[j] = f2bf_rn((x0 * rb(Rb[j]) + x1 * rb(Rb[3 + j])) + x2 * rb(Rb[6 + j]));
+  for (int j = 0; j < 3; ++j) o[j] = f2bf_hw((x0 * rb(Rb[j]) + x1 * rb(Rb[3 + j])) + x2 * rb(Rb[6 + j]));
 }
 
 // out[b][c] = sum_j x[b][j][c], x (B, J, C) bf16, fp32 sums in token order (the focused linear attention's k-sum, transformer.py:560-566)

@@ -13,15 +13,6 @@
 
 namespace unopose {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-__device__ __forceinline__ u16 la_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (u16)(u >> 16);
-}
-__device__ __forceinline__ float la_bf2f(u16 h) { return __uint_as_float(((uint32_t)h) << 16); }
-
 // The focusing of one token row held in MFMA A-operand layout: the lane pair (lane, lane ^ 32) owns the row, lane half `hb` the 8-channel
 // runs [16 ks + 8 hb, +8).  q <- ((relu(x) + 1e-6) / softplus(scale))^3, returns |q_before| / |q_after| (the row's rescale factor).
 __device__ __forceinline__ float la_focus(const u16 *xr, const float *__restrict__ inv_sp, int hb, float (&q)[16][8]) {
@@ -35,7 +26,7 @@ __device__ __forceinline__ float la_focus(const u16 *xr, const float *__restrict
     const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float v = (fmaxf(la_bf2f(f.u[e]), 0.f) + 1e-6f) * sc[e];
+      const float v = (fmaxf(bf2f(f.u[e]), 0.f) + 1e-6f) * sc[e];
       q[ks][e] = v;
       n1 += v * v;
     }
@@ -95,7 +86,7 @@ __global__ __launch_bounds__(256) void linear_attn_kernel(const u16 *__restrict_
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float v = q[ks][e] * fac;
-      f.u[e] = la_f2bf(v);
+      f.u[e] = f2bf(v);
       if (MODE == 0) zp[ks >> 2] += v * ks_b[ks * 16 + e];
     }
     qa[ks] = f.v;
@@ -144,7 +135,7 @@ __global__ __launch_bounds__(256) void linear_attn_kernel(const u16 *__restrict_
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * hb;
-        tile[wave][row][h * 64 + nt * 32 + col] = la_f2bf(acc[r] * zl[wave][row][h]);
+        tile[wave][row][h * 64 + nt * 32 + col] = f2bf(acc[r] * zl[wave][row][h]);
       }
     }
   }
@@ -199,14 +190,14 @@ __global__ __launch_bounds__(256) void linear_attn_kv_state_kernel(const u16 *__
       for (int ks = 0; ks < 16; ++ks) {
         union { bf16x8 v; u16 u[8]; } f;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) f.u[e] = live ? la_f2bf(q[ks][e] * fac) : (u16)0;
+        for (int e = 0; e < 8; ++e) f.u[e] = live ? f2bf(q[ks][e] * fac) : (u16)0;
         *reinterpret_cast<bf16x8 *>(xr + ks * 16) = f.v;  // the positions this lane read: no other lane touches them
       }
     }
     __syncthreads();
     const int valid = min(128, J - r0);
 #pragma unroll 8
-    for (int t = 0; t < valid; ++t) csum += la_bf2f(kf_s[t][tid]);
+    for (int t = 0; t < valid; ++t) csum += bf2f(kf_s[t][tid]);
     const int nk = (valid + 15) >> 4;
 #pragma unroll 2
     for (int kk = 0; kk < nk; ++kk) {
@@ -238,7 +229,7 @@ __global__ __launch_bounds__(256) void linear_attn_kv_state_kernel(const u16 *__
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int d = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb;
-        dst[d * 64 + nt * 32 + col] = la_f2bf(acc[mt][nt][r]);
+        dst[d * 64 + nt * 32 + col] = f2bf(acc[mt][nt][r]);
       }
 }
 
@@ -247,18 +238,6 @@ __global__ __launch_bounds__(256) void linear_attn_kv_state_kernel(const u16 *__
 // MFMAs (x = xh + xl, 3 MFMAs per product, fp32 accumulation: ~2^-16 relative error, as csrc/attn_f32.hip),
 // fp32 in / out.  I/O goes straight between global memory and fragment registers (32-byte pieces per
 // lane): this is the parity configuration, not the benched one.
-__device__ __forceinline__ void la_split(const float (&v)[8], bf16x8 &hi, bf16x8 &lo) {
-  union { bf16x8 v; uint32_t u[4]; } h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    h.u[e] = cvt_pk_bf16_f32(v[2 * e], v[2 * e + 1]);
-    const float r0 = v[2 * e] - __uint_as_float(h.u[e] << 16);
-    const float r1 = v[2 * e + 1] - __uint_as_float(h.u[e] & 0xFFFF0000u);
-    l.u[e] = cvt_pk_bf16_f32(r0, r1);
-  }
-  hi = h.v;
-  lo = l.v;
-}
 
 // x: (B,N,256) fp32 projected q (or k); kvt: (B,4,64 d,64 c) fp32; ksum: (B,256) fp32; out (B,N,256) fp32.
 template <int MODE>
@@ -332,9 +311,9 @@ __global__ __launch_bounds__(256) void linear_attn_f32_kernel(const float *__res
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
   for (int h = 0; h < 4; ++h) {
-    bf16x8 qh[4], ql[4];
+    bf16x8_hl qs[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) la_split(q[h * 4 + ks], qh[ks], ql[ks]);
+    for (int ks = 0; ks < 4; ++ks) qs[ks] = split8_bf16(q[h * 4 + ks]);
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
       f32x16 acc;
@@ -346,11 +325,7 @@ __global__ __launch_bounds__(256) void linear_attn_f32_kernel(const float *__res
         const float4 b0 = *reinterpret_cast<const float4 *>(kp + ks * 16);
         const float4 b1 = *reinterpret_cast<const float4 *>(kp + ks * 16 + 4);
         const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-        bf16x8 bh, bl;
-        la_split(bv, bh, bl);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ql[ks], bh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qh[ks], bl, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qh[ks], bh, acc, 0, 0, 0);
+        acc = mfma3_lh_hl_hh_32x32(qs[ks], split8_bf16(bv), acc);
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {

@@ -19,8 +19,6 @@ namespace unopose {
 
 constexpr int PE_SCAN_STEPS = 4;  // 64-candidate steps of the ball query per loop trip (measured against 1 step per trip)
 
-typedef unsigned short u16;
-
 // channel held by accumulator register r of half-wave h in the 32x32 C/D layout
 __device__ __forceinline__ int cd_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
@@ -327,15 +325,6 @@ __global__ __launch_bounds__(256) void pe_group_mlp_max_kernel(
 // accumulator registers 8s..8s+7 of a 32x32 C/D tile hold, per half-wave hb, the channels
 // 16s + (e&3) + 8(e>>2) + 4hb (e = 0..7) -- exactly one 16-wide k-step of the next layer -- so the
 // weights are stored with their input channels permuted to k' = 16s + 8hb + e.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ u16 pe_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (u16)(u >> 16);
-}
-__device__ __forceinline__ float pe_bf2f(u16 h) { return __uint_as_float(((uint32_t)h) << 16); }
-
 __device__ __forceinline__ int pe_kperm(int c) {  // input channel -> position in the permuted k order
   const int cc = c & 15;
   return (c & ~15) + ((cc >> 2) & 1) * 8 + (cc & 3) + 4 * (cc >> 3);
@@ -348,31 +337,6 @@ struct PeLdsB {
   float b1[32], b2[64], b3[128];
 };
 
-// gfx950 packed fp32 -> bf16 conversion (RNE): low half = cvt(a), high half = cvt(b)
-__device__ __forceinline__ uint32_t pe_cvt_pk(float a, float b) {
-  return cvt_pk_bf16_f32(a, b);
-}
-
-// split 8 fp32 values into packed bf16 hi / lo fragments: v ~ hi + lo
-__device__ __forceinline__ void pe_split8(const float *v, bf16x8 &hi, bf16x8 &lo) {
-  union { bf16x8 v; uint32_t w[4]; } H, Lo;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const uint32_t h = pe_cvt_pk(v[2 * e], v[2 * e + 1]);
-    H.w[e] = h;
-    const float r0 = v[2 * e] - __uint_as_float(h << 16);
-    const float r1 = v[2 * e + 1] - __uint_as_float(h & 0xFFFF0000u);
-    Lo.w[e] = pe_cvt_pk(r0, r1);
-  }
-  hi = H.v;
-  lo = Lo.v;
-}
-
-#define PE_MFMA3(acc, ah, al, bh, bl)                                       \
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);      \
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);      \
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0)
-
 // One-time packing of the folded fp32 weights into the LDS image of the bf16x3 kernel.
 __global__ __launch_bounds__(256) void pe_pack_weights_kernel(const float *__restrict__ w1, const float *__restrict__ b1,
                                                               const float *__restrict__ w2, const float *__restrict__ b2,
@@ -382,24 +346,24 @@ __global__ __launch_bounds__(256) void pe_pack_weights_kernel(const float *__res
   for (int e = tid; e < 32 * 16; e += 256) {
     const int o = e >> 4, kk = e & 15;
     const float v = kk < 6 ? w1[o * 6 + kk] : 0.f;
-    const u16 h = pe_f2bf(v);
+    const u16 h = f2bf(v);
     L->w1h[o][kk] = h;
-    L->w1l[o][kk] = pe_f2bf(v - pe_bf2f(h));
+    L->w1l[o][kk] = f2bf(v - bf2f(h));
   }
   for (int e = tid; e < 64 * 32; e += 256) {
     const int o = e >> 5, c = e & 31;
     const float v = w2[e];
-    const u16 h = pe_f2bf(v);
+    const u16 h = f2bf(v);
     L->w2h[o][pe_kperm(c)] = h;
-    L->w2l[o][pe_kperm(c)] = pe_f2bf(v - pe_bf2f(h));
+    L->w2l[o][pe_kperm(c)] = f2bf(v - bf2f(h));
   }
   for (int e = tid; e < 128 * 64; e += 256) {
     const int o = e >> 6, c = e & 63;
     const float v = w3[e];
-    const u16 h = pe_f2bf(v);
+    const u16 h = f2bf(v);
     const int kp = pe_kperm(c) ^ ((o & 7) << 3);  // swizzle the 8-element (16-byte) slot
     L->w3h[o][kp] = h;
-    L->w3l[o][kp] = pe_f2bf(v - pe_bf2f(h));
+    L->w3l[o][kp] = f2bf(v - bf2f(h));
   }
   if (tid < 32) L->b1[tid] = b1[tid];
   if (tid < 64) L->b2[tid] = b2[tid];
@@ -550,26 +514,25 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] = 0.f;  // k' 8..15 of the padded first layer
       }
-      bf16x8 xh, xl;
-      pe_split8(f, xh, xl);
+      const bf16x8_hl x = split8_bf16(f);
       // The weight fragments and bias values of the NEXT group of MFMAs are read from LDS (into the other of two register sets) before
       // the current group is issued: left to the compiler every k-step's two fragments were read right in front of their three MFMAs
       // -- ~20 exposed LDS round trips per tile (round 4: the tile loop was latency-bound, the matrix pipe 36 % busy).
       struct Grp {
-        bf16x8 h[4], l[4];
+        bf16x8_hl w[4];
         float4 b[4];
       } ga, gb;
       auto load_l1 = [&](Grp &g) {
-        g.h[0] = *reinterpret_cast<const bf16x8 *>(&L->w1h[col][half * 8]);
-        g.l[0] = *reinterpret_cast<const bf16x8 *>(&L->w1l[col][half * 8]);
+        g.w[0].hi = *reinterpret_cast<const bf16x8 *>(&L->w1h[col][half * 8]);
+        g.w[0].lo = *reinterpret_cast<const bf16x8 *>(&L->w1l[col][half * 8]);
 #pragma unroll
         for (int q = 0; q < 4; ++q) g.b[q] = *reinterpret_cast<const float4 *>(&L->b1[8 * q + 4 * half]);
       };
       auto load_l2 = [&](Grp &g, int ot) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          g.h[ks] = *reinterpret_cast<const bf16x8 *>(&L->w2h[ot * 32 + col][ks * 16 + half * 8]);
-          g.l[ks] = *reinterpret_cast<const bf16x8 *>(&L->w2l[ot * 32 + col][ks * 16 + half * 8]);
+          g.w[ks].hi = *reinterpret_cast<const bf16x8 *>(&L->w2h[ot * 32 + col][ks * 16 + half * 8]);
+          g.w[ks].lo = *reinterpret_cast<const bf16x8 *>(&L->w2l[ot * 32 + col][ks * 16 + half * 8]);
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) g.b[q] = *reinterpret_cast<const float4 *>(&L->b2[ot * 32 + 8 * q + 4 * half]);
@@ -579,8 +542,8 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
           const int kp = (ks * 16 + half * 8) ^ ((row & 7) << 3);
-          g.h[ks] = *reinterpret_cast<const bf16x8 *>(&L->w3h[row][kp]);
-          g.l[ks] = *reinterpret_cast<const bf16x8 *>(&L->w3l[row][kp]);
+          g.w[ks].hi = *reinterpret_cast<const bf16x8 *>(&L->w3h[row][kp]);
+          g.w[ks].lo = *reinterpret_cast<const bf16x8 *>(&L->w3l[row][kp]);
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) g.b[q] = *reinterpret_cast<const float4 *>(&L->b3[ot * 32 + 8 * q + 4 * half]);
@@ -594,14 +557,14 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
           h[4 * q + 3] = g.b[q].w;
         }
       };
-      bf16x8 a1h[2], a1l[2], a2h[4], a2l[4];
-      auto relu_split = [&](const f32x16 &h, bf16x8 *oh, bf16x8 *ol) {
+      bf16x8_hl a1[2], a2[4];
+      auto relu_split = [&](const f32x16 &h, bf16x8_hl *o) {
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
           float v[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = fmaxf(h[s2 * 8 + e], 0.f);
-          pe_split8(v, oh[s2], ol[s2]);
+          o[s2] = split8_bf16(v);
         }
       };
       load_l1(ga);
@@ -610,25 +573,25 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
       {
         f32x16 h1;
         init(h1, ga);
-        PE_MFMA3(h1, ga.h[0], ga.l[0], xh, xl);
+        h1 = mfma3_hh_hl_lh_32x32(ga.w[0], x, h1);
         load_l2(ga, 1);
         __builtin_amdgcn_sched_barrier(0);
-        relu_split(h1, a1h, a1l);
+        relu_split(h1, a1);
       }
       {
         f32x16 h2;
         init(h2, gb);
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) { PE_MFMA3(h2, gb.h[ks], gb.l[ks], a1h[ks], a1l[ks]); }
+        for (int ks = 0; ks < 2; ++ks) h2 = mfma3_hh_hl_lh_32x32(gb.w[ks], a1[ks], h2);
         load_l3(gb, 0);
         __builtin_amdgcn_sched_barrier(0);
-        relu_split(h2, a2h, a2l);
+        relu_split(h2, a2);
         init(h2, ga);
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) { PE_MFMA3(h2, ga.h[ks], ga.l[ks], a1h[ks], a1l[ks]); }
+        for (int ks = 0; ks < 2; ++ks) h2 = mfma3_hh_hl_lh_32x32(ga.w[ks], a1[ks], h2);
         load_l3(ga, 1);
         __builtin_amdgcn_sched_barrier(0);
-        relu_split(h2, a2h + 2, a2l + 2);
+        relu_split(h2, a2 + 2);
       }
 #pragma unroll
       for (int ot = 0; ot < 4; ++ot) {
@@ -638,7 +601,7 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
         f32x16 h3;
         init(h3, g);
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) { PE_MFMA3(h3, g.h[ks], g.l[ks], a2h[ks], a2l[ks]); }
+        for (int ks = 0; ks < 4; ++ks) h3 = mfma3_hh_hl_lh_32x32(g.w[ks], a2[ks], h3);
         if (ot + 2 < 4) {
           load_l3(g, ot + 2);  // (into the set the MFMAs above have just read: the hardware keeps the order)
           __builtin_amdgcn_sched_barrier(0);
@@ -675,13 +638,12 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
         const int d = lane + 64 * q, blk = d >> 5, w = d & 31, k = blk * 32 + (w & 15) * 2;
         const float v0 = stage[k], v1 = stage[k + 1];
         const uint32_t h = cvt_pk_bf16_f32(v0, v1);
-        O32[d] = (w & 16) ? cvt_pk_bf16_f32(v0 - __uint_as_float(h << 16), v1 - __uint_as_float(h & 0xffff0000u)) : h;
+        O32[d] = (w & 16) ? cvt_pk_bf16_lo(v0, v1, h) : h;
       }
     }
     __builtin_amdgcn_wave_barrier();
   }
 }
-#undef PE_MFMA3
 
 }  // namespace unopose
 

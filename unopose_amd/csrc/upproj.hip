@@ -22,10 +22,6 @@
 
 namespace unopose {
 
-typedef unsigned short u16;
-
-__device__ __forceinline__ float up_bf2f(u16 h) { return __uint_as_float((uint32_t)h << 16); }
-
 // flags <- 0 and row_list <- -1 in ONE launch (two hipMemsetAsync cost two ~50-us runtime fill kernels in front of every plan)
 __global__ __launch_bounds__(256) void upproj_clear_kernel(int *__restrict__ flags, long nflags, int *__restrict__ row_list, long nrows) {
   const long n = nflags + nrows, step = (long)gridDim.x * 256;
@@ -143,10 +139,10 @@ __global__ __launch_bounds__(256) void bilinear_sample_compact_kernel(const u16 
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const uint2 r = *reinterpret_cast<const uint2 *>(Cc + (size_t)rows[k] * 256 + lane * 4);
-    v[k][0] = up_bf2f((u16)(r.x & 0xFFFF));
-    v[k][1] = up_bf2f((u16)(r.x >> 16));
-    v[k][2] = up_bf2f((u16)(r.y & 0xFFFF));
-    v[k][3] = up_bf2f((u16)(r.y >> 16));
+    v[k][0] = bf2f((u16)(r.x & 0xFFFF));
+    v[k][1] = bf2f((u16)(r.x >> 16));
+    v[k][2] = bf2f((u16)(r.y & 0xFFFF));
+    v[k][3] = bf2f((u16)(r.y >> 16));
   }
   const float ly = tp.ly, lx = tp.lx;
   float4 res;

@@ -18,12 +18,6 @@ namespace unopose {
 
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ u16 va_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (u16)(u >> 16);
-}
-
 constexpr int VA_CHUNK = 128;            // keys staged per LDS chunk
 constexpr int VA_LDK = 64 + 8;           // padded row of the K chunk  [key][channel]
 // V chunk image: 4 sub-tiles [128 keys][16 channels] (row = 32 B), sub-tile stride 4224 B.  Read with the
@@ -37,9 +31,6 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 // The 4 waves of a workgroup share one (image, head): K and V of a 128-key chunk are loaded once with
 // coalesced 16-byte reads, K kept row-major and V transposed on the way into LDS (so the caller needs no
 // V^T copy), then every wave runs its 32 queries against the chunk.
-__device__ __forceinline__ uint32_t va_cvt_pk(float a, float b) {  // packed RNE fp32 -> bf16 (gfx950)
-  return cvt_pk_bf16_f32(a, b);
-}
 
 constexpr float VA_DEFER = 8.f;  // log2 of the largest P the deferred rescale lets through
 constexpr int VA_BUF = VA_CHUNK * VA_LDK + 4 * VA_VSUB;  // u16 per chunk buffer (K rows + V sub-tiles)
@@ -190,7 +181,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(QB == 1
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) pf[qb][s2].w[e] = va_cvt_pk(s[qb][s2 * 8 + 2 * e], s[qb][s2 * 8 + 2 * e + 1]);
+        for (int e = 0; e < 4; ++e) pf[qb][s2].w[e] = cvt_pk_bf16_f32(s[qb][s2 * 8 + 2 * e], s[qb][s2 * 8 + 2 * e + 1]);
     }
     // ---- O^T += V^T P^T ; k-step s2 = accumulator registers 8*s2 .. 8*s2+7 of S (permuted key order that
     // the V fragment reads follow); A = V^T: row = channel t*32 + col, keys kt + 16 s2 + 4 hb + {0..3}, + 8
@@ -283,7 +274,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(QB == 1
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int c = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb;
-        Ot[wave][col][c] = va_f2bf(o[qb][t][r] * inv);
+        Ot[wave][col][c] = f2bf(o[qb][t][r] * inv);
       }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -434,7 +425,7 @@ __global__ __launch_bounds__(NW * 64, 2) void vit_attn_kernel_dma(const u16 *__r
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) pf[qb][s2].w[e] = va_cvt_pk(s[qb][s2 * 8 + 2 * e], s[qb][s2 * 8 + 2 * e + 1]);
+        for (int e = 0; e < 4; ++e) pf[qb][s2].w[e] = cvt_pk_bf16_f32(s[qb][s2 * 8 + 2 * e], s[qb][s2 * 8 + 2 * e + 1]);
     }
     auto v_frag = [&](int s2, int t) {
       const char *vp = vlane + t * 2 * VD_VSUBB + (kt + s2 * 16) * 32;
@@ -493,7 +484,7 @@ __global__ __launch_bounds__(NW * 64, 2) void vit_attn_kernel_dma(const u16 *__r
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) Ot[wave][col][t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb] = va_f2bf(o[qb][t][r] * inv);
+      for (int r = 0; r < 16; ++r) Ot[wave][col][t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb] = f2bf(o[qb][t][r] * inv);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");

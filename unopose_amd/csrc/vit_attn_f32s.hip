@@ -28,14 +28,6 @@ constexpr int VS_BUFB = 2 * VS_KPLANE + 2 * VS_VPLANE;  // 66560 B
 constexpr float VS_DEFER = 8.f;  // log2 of the largest P the deferred rescale lets through
 constexpr int VS_NW = 12;  // wavefronts per workgroup = 3 per SIMD (154 VGPRs); 8: 1189 us, 12: 1086 us at 64 x 12 x 1374
 
-struct HLf {
-  bf16x8 h, l;
-};
-#define VS_MFMA3(acc, a, b)                                          \
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, acc, 0, 0, 0); \
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.l, acc, 0, 0, 0); \
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, acc, 0, 0, 0)
-
 // qkv_s: (B, T) token rows of 3 * H * 64 values in the split layout (3 * H * 256 bytes per token: q blocks | k blocks | v blocks,
 // head h = blocks 2h, 2h + 1 of each third); out_s: (B, T) rows of H * 64 values in the split layout.
 template <int NW>
@@ -87,19 +79,19 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
   };
   const int nchunks = (T + VS_CHUNK - 1) / VS_CHUNK;
   issue_chunk(0, 0);
-  HLf qf[4];
+  bf16x8_hl qf[4];
   {
     const char *qp = base + (size_t)min(q0 + col, T - 1) * RB + qoff;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int c = ks * 16 + hb * 8;  // channels c .. c + 7
       const char *p = qp + (c >> 5) * 128 + (c & 31) * 2;
-      qf[ks].h = *reinterpret_cast<const bf16x8 *>(p);
-      qf[ks].l = *reinterpret_cast<const bf16x8 *>(p + 64);
+      qf[ks].hi = *reinterpret_cast<const bf16x8 *>(p);
+      qf[ks].lo = *reinterpret_cast<const bf16x8 *>(p + 64);
     }
   }
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(qf[ks].h), "+v"(qf[ks].l));  // the Q loads are complete HERE (see vit_attn.hip)
+  for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(qf[ks].hi), "+v"(qf[ks].lo));  // the Q loads are complete HERE (see vit_attn.hip)
   f32x16 o[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
@@ -119,16 +111,16 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
     // all eight K fragments first, then the twelve MFMAs (the compiler otherwise reads every k-step's pair right in front of its MFMAs:
     // four exposed LDS round trips instead of one)
-    HLf kf[4];
+    bf16x8_hl kf[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const char *kp = buf + kt * 128 + kfo[ks];
-      kf[ks].h = *reinterpret_cast<const bf16x8 *>(kp);
-      kf[ks].l = *reinterpret_cast<const bf16x8 *>(kp + VS_KPLANE);
+      kf[ks].hi = *reinterpret_cast<const bf16x8 *>(kp);
+      kf[ks].lo = *reinterpret_cast<const bf16x8 *>(kp + VS_KPLANE);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) { VS_MFMA3(s, kf[ks], qf[ks]); }
+    for (int ks = 0; ks < 4; ++ks) s = mfma3_lh_hl_hh_32x32(kf[ks], qf[ks], s);
     if (partial) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
@@ -138,7 +130,7 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
   auto softmax_pv_tile = [&](const char *buf, int kt, f32x16 &s) {
     // the tile's V fragments are read before the softmax arithmetic (measured: each read in front of its MFMAs 1101 us, all fragments of a
     // product before its MFMAs 1086 us, the V fragments before the softmax 1079 us)
-    HLf vfe[2][2];
+    bf16x8_hl vfe[2][2];
     {
       const char *vl0 = buf + vlane_off;
 #pragma unroll
@@ -151,7 +143,7 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
           vh.h4[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + 8 * 32));
           vl.h4[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + VS_VPLANE));
           vl.h4[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + VS_VPLANE + 8 * 32));
-          vfe[s2][t] = HLf{vh.v, vl.v};
+          vfe[s2][t] = bf16x8_hl{vh.v, vl.v};
         }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -174,19 +166,14 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
     const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(ls), __float_as_uint(ls), false, false);
     l_run = fmaf(l_run, alpha, __uint_as_float(sw[0]) + __uint_as_float(sw[1]));
     // P = hi + lo, packed as the B operand of the two 16-key k-steps
-    union PF {
-      bf16x8 v;
-      uint32_t w[4];
-    } ph[2], pl[2];
+    bf16x8_hl pf[2];
 #pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2)
+    for (int s2 = 0; s2 < 2; ++s2) {
+      float pv[8];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float a = s[s2 * 8 + 2 * e], c = s[s2 * 8 + 2 * e + 1];
-        const uint32_t hw = cvt_pk_bf16_f32(a, c);
-        ph[s2].w[e] = hw;
-        pl[s2].w[e] = cvt_pk_bf16_f32(a - __uint_as_float(hw << 16), c - __uint_as_float(hw & 0xffff0000u));
-      }
+      for (int e = 0; e < 8; ++e) pv[e] = s[s2 * 8 + e];
+      pf[s2] = split8_bf16(pv);
+    }
     const char *vlane = buf + vlane_off;
     auto v_frag = [&](int s2, int t) {
       const char *vp = vlane + t * 2 * VS_VSUBB + (kt + s2 * 16) * 32;
@@ -198,16 +185,13 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
       vh.h4[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + 8 * 32));
       vl.h4[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + VS_VPLANE));
       vl.h4[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + VS_VPLANE + 8 * 32));
-      return HLf{vh.v, vl.v};
+      return bf16x8_hl{vh.v, vl.v};
     };
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const HLf pf{ph[s2].v, pl[s2].v};
-        VS_MFMA3(o[t], vfe[s2][t], pf);
-      }
+      for (int t = 0; t < 2; ++t) o[t] = mfma3_lh_hl_hh_32x32(vfe[s2][t], pf[s2], o[t]);
     if (__builtin_expect(__any(grow), 0)) {  // rare after the first tile: O = (O - D) alpha + D with D = this tile's P.V (vit_attn.hip)
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -215,11 +199,7 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
 #pragma unroll
         for (int r = 0; r < 16; ++r) d[r] = 0.f;
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const HLf vf = v_frag(s2, t);
-          const HLf pf{ph[s2].v, pl[s2].v};
-          VS_MFMA3(d, vf, pf);
-        }
+        for (int s2 = 0; s2 < 2; ++s2) d = mfma3_lh_hl_hh_32x32(v_frag(s2, t), pf[s2], d);
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[t][r] = fmaf(o[t][r] - d[r], alpha, d[r]);
       }
@@ -266,8 +246,8 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
       uint2 hi, lo;
       hi.x = cvt_pk_bf16_f32(v.x, v.y);
       hi.y = cvt_pk_bf16_f32(v.z, v.w);
-      lo.x = cvt_pk_bf16_f32(v.x - __uint_as_float(hi.x << 16), v.y - __uint_as_float(hi.x & 0xffff0000u));
-      lo.y = cvt_pk_bf16_f32(v.z - __uint_as_float(hi.y << 16), v.w - __uint_as_float(hi.y & 0xffff0000u));
+      lo.x = cvt_pk_bf16_lo(v.x, v.y, hi.x);
+      lo.y = cvt_pk_bf16_lo(v.z, v.w, hi.y);
       const int c = seg * 4;  // channel inside the head
       char *line = out_s + ((size_t)b * T + q0 + row) * ORB + h * 256 + (c >> 5) * 128 + (c & 31) * 2;
       *reinterpret_cast<uint2 *>(line) = hi;
