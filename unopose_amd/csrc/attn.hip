@@ -242,7 +242,8 @@ __global__ __launch_bounds__(256, 2) void token_attn_rpe_dma_kernel(const u16 *_
   const int rows_w = rw_here;                    // query rows of this tile
   const int total = rows_w * nt_valid;            // tiles of the wave's stream
   // whole-tensor descriptor: the last tile of the last query row reads past m keys -- into the next row's block, or (very last row) past
-  // the end: zeros.  Keys >= m are masked in the softmax.
+  // the end: zeros.  Keys >= m are masked in the softmax.  The whole byte offset goes in the VGPR: the range check covers the vector
+  // offset, not the scalar one (as in gemm_small.hip).  (An offset that wraps past 2^32 lands in E's first 7.5 KiB: in range, masked.)
   const __amdgpu_buffer_rsrc_t e_rs = __builtin_amdgcn_make_buffer_rsrc((void *)E, 0, (int)min((size_t)B * n * m * 512, (size_t)0xFFFFFFFFu), 0x00020000);
   // piece j of a tile = keys 2 j + (lane >> 5): source byte = key * 512 + (((lane & 31) ^ key) << 4)  (key < 16: XOR of the low 4 chunk bits)
   uint32_t voff[8];
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_rpe_dma_kernel(const u16 *_
     const uint32_t so = row0 + (uint32_t)r * (uint32_t)m * 512u + (uint32_t)t * 8192u;
     const uint32_t dst = lds0 + (uint32_t)(s & 1) * 8192u;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) gemm_dma16<TA_EPOL>(dst + j * 1024, voff[j], e_rs, (int)so);
+    for (int j = 0; j < 8; ++j) gemm_dma16<TA_EPOL>(dst + j * 1024, so + voff[j], e_rs, 0);
   };
   issue_tile(0);
   if (total > 1) issue_tile(1);

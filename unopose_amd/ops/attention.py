@@ -140,7 +140,7 @@ def _attn_weights(att, rpe):
     cache = getattr(att, "_hip_cache", None)
     if cache is not None and cache[0] == key:
         return cache[1]
-    with torch.no_grad():
+    with torch.no_grad(), torch.autocast("cuda", enabled=False):  # (the caller runs under autocast: its einsum would fold in bf16)
         bf = torch.bfloat16
         wq, bq = att.proj_q.weight.float(), att.proj_q.bias.float()
         parts_w, parts_b = [wq], [bq]
