@@ -400,6 +400,21 @@ int unopose_token_attention_f32(const float *q, int ldq, const float *k, int ldk
                                 const float *qp, int ldqp, const float *E, int B, int n, int m,
                                 float scale, float *out, unopose_stream_t stream);
 int unopose_vit_attention_f32(const float *qkv, int B, int T, int H, float *out, unopose_stream_t stream);
+/* Token attention under autograd (the training step, float32).  _train: unopose_token_attention_f32 (the same
+ * arithmetic: out is bit-identical) that also writes P (B,4,n,KP) = the softmax weights, zero on the padded keys.
+ * _backward: given dout (B,n,256) contiguous and the forward's P, writes dq (B,n,256), dk / dv (B,m,256) and, with
+ * RPE, dqp (B,n,4,256) and dE (B,n,m,256), all contiguous, plus the workspace dS (B,4,n,KP) = the score gradient
+ * before the scale.  v (B,m,256) with row stride ldv; kt (B,256,KP) = k transposed and zero-padded like vt; qp / E
+ * as in the forward; dE may be NULL (E still read for dqp).  dS (through dout v^T) and dq use the forward's hi / lo-
+ * split MFMAs; dqp, dE, dk and dv are exact fp32 FMAs.  No atomics: two calls give the same bits.  E is read once,
+ * dE written once. */
+int unopose_token_attention_f32_train(const float *q, int ldq, const float *k, int ldk, const float *vt,
+                                      const float *qp, int ldqp, const float *E, int B, int n, int m,
+                                      float scale, float *out, float *P, unopose_stream_t stream);
+int unopose_token_attention_f32_backward(const float *dout, const float *q, int ldq, const float *v, int ldv,
+                                         const float *kt, const float *qp, int ldqp, const float *E, const float *P,
+                                         int B, int n, int m, float scale, float *dS, float *dq, float *dk, float *dv,
+                                         float *dqp, float *dE, unopose_stream_t stream);
 /* The same with the output in the split layout of unopose_linear_f32x3 ((B,T,2 H 64) bf16: the operand of the projection that
  * follows, timm Attention.proj). */
 int unopose_vit_attention_f32_split(const float *qkv, int B, int T, int H, void *out_split, unopose_stream_t stream);

@@ -57,6 +57,8 @@ SIGNATURES = {
     "unopose_token_attention": [_P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _F, _P, _P],
     "unopose_token_attention_key_pad": [],
     "unopose_token_attention_f32": [_P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _F, _P, _P],
+    "unopose_token_attention_f32_train": [_P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _F, _P, _P, _P],
+    "unopose_token_attention_f32_backward": [_P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P],
     "unopose_vit_attention_f32": [_P, _I, _I, _I, _P, _P],
     "unopose_vit_attention_f32_split": [_P, _I, _I, _I, _P, _P],
     "unopose_vit_attention_f32_ss": [_P, _I, _I, _I, _P, _P],

@@ -29,13 +29,14 @@ constexpr int AF_NT = 14, AF_MP = AF_NT * 16;
 constexpr int AF_PF_DEPTH = 4;  // operand pairs in flight ahead of the MFMAs of the token attention
 
 // ---- token attention (see attn.hip for the scheme): one wave = 4 query rows x 4 heads ----------------
-template <bool RPE>
+// STORE_P (training forward): P is also written to pst (B,4,n,AF_MP), zero on the padded keys, for the backward below.
+template <bool RPE, bool STORE_P = false>
 __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__restrict__ q, int ldq,
                                                              const float *__restrict__ k, int ldk,
                                                              const float *__restrict__ vt,
                                                              const float *__restrict__ qp, int ldqp,
                                                              const float *__restrict__ E, int n, int m, float scale,
-                                                             float *__restrict__ out) {
+                                                             float *__restrict__ out, float *__restrict__ pst) {
   __shared__ __attribute__((aligned(16))) float Pl[4][16][AF_MP + 4];
   const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n0 = (blockIdx.x * 4 + wave) * 4;
@@ -149,6 +150,13 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
   for (int t = 0; t < AF_NT; ++t)
 #pragma unroll
     for (int h = 0; h < 4; ++h) Pl[wave][kg * 4 + h][t * 16 + li] = acc[t][h] * sm[h];
+  if (STORE_P && n0 + kg < n) {
+    float *Pr = pst + ((size_t)b * 4 * n + n0 + kg) * AF_MP + li;
+#pragma unroll
+    for (int t = 0; t < AF_NT; ++t)
+#pragma unroll
+      for (int h = 0; h < 4; ++h) Pr[(size_t)h * n * AF_MP + t * 16] = acc[t][h] * sm[h];
+  }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -174,6 +182,223 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
       if (ks == NKS - 1 && n0 + kg < n) out[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = o[nt >> 2];
     }
   }
+}
+
+// ---- token attention backward (training): S = scale (q k^T [+ qp . E]), P = softmax(S), O = P v; given dO:
+//   dP = dO v^T, delta = rowsum(P dP) (= rowsum(dO O)), dS = P (dP - delta)
+//   dq = scale dS k, dk = scale dS^T q, dv = P^T dO, dqp = scale dS E, dE = scale sum_h dS_h qp_h
+// Three kernels, each output element owned by one thread (no atomics): dq + dS (the forward's scheme: hi / lo-split MFMAs), the RPE terms
+// (E streamed once, dE written once; exact fp32 FMA: 8 per element of E, far under the memory time) and dk / dv (fp32 FMA, LDS tiles).
+
+// One wave = 4 query rows x 4 heads, as in the forward.  P: the forward's (B,4,n,AF_MP) (zero on padded keys, so dS is too);
+// kt (B,256,AF_MP) = k^T zero-padded.  Writes dS (B,4,n,AF_MP) and dq (B,n,256).
+__global__ __launch_bounds__(256) void token_attn_f32_bwd_dq_kernel(const float *__restrict__ dout, const float *__restrict__ v, int ldv,
+                                                                    const float *__restrict__ P, const float *__restrict__ kt, int n, int m,
+                                                                    float scale, float *__restrict__ dS, float *__restrict__ dq) {
+  __shared__ __attribute__((aligned(16))) float Sl[4][16][AF_MP + 4];
+  const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n0 = (blockIdx.x * 4 + wave) * 4;
+  if (n0 >= n) return;
+  const int li = lane & 15, kg = lane >> 4;
+  const int a_nl = li >> 2, a_h = li & 3;
+  const bool a_valid = n0 + a_nl < n, row_ok = n0 + kg < n;
+  const float *G = dout + ((size_t)b * n + n0 + a_nl) * 256;
+  const float *V = v + (size_t)b * m * ldv;
+  struct Raw {
+    float4 a, b;
+  };
+  auto ld8 = [](const float *p) { return Raw{*reinterpret_cast<const float4 *>(p), *reinterpret_cast<const float4 *>(p + 4)}; };
+  auto sp8 = [](const Raw &r) {
+    const float v[8] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w};
+    return split8_bf16(v);
+  };
+  constexpr int AF_PF = AF_PF_DEPTH, NPAIR = 8 * AF_NT;
+  // dP: the forward's score loop with (dO, v) in place of (q, k)
+  f32x4 acc[AF_NT];
+#pragma unroll
+  for (int t = 0; t < AF_NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int nt_valid = (m + 15) >> 4;
+  {
+    auto addr = [&](int i) { return V + (size_t)min((i % AF_NT) * 16 + li, m - 1) * ldv + (i / AF_NT) * 32 + kg * 8; };
+    Raw ring[AF_PF];
+#pragma unroll
+    for (int i = 0; i < AF_PF; ++i) ring[i] = ld8(addr(i));
+    bf16x8_hl a = af_zero();
+#pragma unroll
+    for (int i = 0; i < NPAIR; ++i) {
+      const int ks = i / AF_NT, t = i % AF_NT;
+      if (t == 0) {
+        const int kk = ks * 32 + kg * 8;
+        a = af_zero();
+        if (a_valid && (kk >> 6) == a_h) a = af_load8(G + kk);
+      }
+      const Raw cur = ring[i % AF_PF];
+      if (i + AF_PF < NPAIR) ring[i % AF_PF] = ld8(addr(i + AF_PF));
+      if (t < nt_valid) acc[t] = mfma3_hh_hl_lh_16x16(a, sp8(cur), acc[t]);
+    }
+  }
+  // acc[t][h]: dP of query n0 + kg, head h, key t * 16 + li
+  const size_t hstride = (size_t)n * AF_MP;
+  const size_t prow = ((size_t)b * 4 * n + n0 + kg) * AF_MP + li;
+  float p[AF_NT][4], dl[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < AF_NT; ++t)
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      p[t][h] = row_ok ? P[prow + h * hstride + t * 16] : 0.f;
+      dl[h] = fmaf(p[t][h], acc[t][h], dl[h]);
+    }
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    float v = dl[h];
+    v += af_swz<1>(v); v += af_swz<2>(v); v += af_swz<4>(v); v += af_swz<8>(v);
+    dl[h] = v;
+  }
+#pragma unroll
+  for (int t = 0; t < AF_NT; ++t)
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      const float ds = p[t][h] * (acc[t][h] - dl[h]);
+      Sl[wave][kg * 4 + h][t * 16 + li] = ds;
+      if (row_ok) dS[prow + h * hstride + t * 16] = ds;
+    }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  // dq: the forward's P v loop with (dS, k^T) in place of (P, v^T)
+  bf16x8_hl sa[AF_MP / 32];
+#pragma unroll
+  for (int ks = 0; ks < AF_MP / 32; ++ks) sa[ks] = af_load8(&Sl[wave][li][ks * 32 + kg * 8]);
+  const float *KT = kt + (size_t)b * 256 * AF_MP;
+  {
+    constexpr int NKS = AF_MP / 32, NP2 = 16 * NKS;
+    auto addr = [&](int i) { return KT + (size_t)((i / NKS) * 16 + li) * AF_MP + kg * 8 + (i % NKS) * 32; };
+    Raw ring[AF_PF];
+#pragma unroll
+    for (int i = 0; i < AF_PF; ++i) ring[i] = ld8(addr(i));
+    f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < NP2; ++i) {
+      const int nt = i / NKS, ks = i % NKS;
+      if (ks == 0) o = f32x4{0.f, 0.f, 0.f, 0.f};
+      const Raw cur = ring[i % AF_PF];
+      if (i + AF_PF < NP2) ring[i % AF_PF] = ld8(addr(i + AF_PF));
+      o = mfma3_hh_hl_lh_16x16(sa[ks], sp8(cur), o);
+      if (ks == NKS - 1 && row_ok) dq[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = o[nt >> 2] * scale;
+    }
+  }
+}
+
+// RPE terms: one wave per query row i; lane l owns channels 4 l .. 4 l + 3 of every key's E row (one coalesced 1 KiB row per key).
+// dqp (B,n,1024) contiguous; dE may be null (no gradient wanted: E is still read for dqp).
+constexpr int AB_UNROLL = 8;  // E rows in flight per wave
+__global__ __launch_bounds__(256) void token_attn_f32_bwd_rpe_kernel(const float *__restrict__ dS, const float *__restrict__ qp, int ldqp,
+                                                                     const float *__restrict__ E, int n, int m, float scale,
+                                                                     float *__restrict__ dqp, float *__restrict__ dE) {
+  __shared__ __attribute__((aligned(16))) float4 Sl[4][AF_MP];  // [wave][key]: scale dS of the 4 heads
+  const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x * 4 + wave;
+  if (i >= n) return;
+  const size_t row = (size_t)b * n + i, hstride = (size_t)n * AF_MP;
+  const float *S = dS + ((size_t)b * 4 * n + i) * AF_MP;
+  for (int j = lane; j < m; j += 64)
+    Sl[wave][j] = make_float4(scale * S[j], scale * S[hstride + j], scale * S[2 * hstride + j], scale * S[3 * hstride + j]);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  float4 qv[4], acc[4];
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    qv[h] = *reinterpret_cast<const float4 *>(qp + row * ldqp + h * 256 + lane * 4);
+    acc[h] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const float *Er = E + row * (size_t)m * 256 + lane * 4;
+  float *dEr = dE ? dE + row * (size_t)m * 256 + lane * 4 : nullptr;
+  auto step = [&](int j, const float4 &e) {
+    const float4 s = Sl[wave][j];
+    const float sh[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      acc[h].x = fmaf(sh[h], e.x, acc[h].x);
+      acc[h].y = fmaf(sh[h], e.y, acc[h].y);
+      acc[h].z = fmaf(sh[h], e.z, acc[h].z);
+      acc[h].w = fmaf(sh[h], e.w, acc[h].w);
+    }
+    if (dEr) {
+      float4 d = make_float4(sh[0] * qv[0].x, sh[0] * qv[0].y, sh[0] * qv[0].z, sh[0] * qv[0].w);
+#pragma unroll
+      for (int h = 1; h < 4; ++h) {
+        d.x = fmaf(sh[h], qv[h].x, d.x);
+        d.y = fmaf(sh[h], qv[h].y, d.y);
+        d.z = fmaf(sh[h], qv[h].z, d.z);
+        d.w = fmaf(sh[h], qv[h].w, d.w);
+      }
+      *reinterpret_cast<float4 *>(dEr + (size_t)j * 256) = d;
+    }
+  };
+  int j = 0;
+  for (; j + AB_UNROLL <= m; j += AB_UNROLL) {
+    float4 e[AB_UNROLL];
+#pragma unroll
+    for (int u = 0; u < AB_UNROLL; ++u) e[u] = *reinterpret_cast<const float4 *>(Er + (size_t)(j + u) * 256);
+#pragma unroll
+    for (int u = 0; u < AB_UNROLL; ++u) step(j + u, e[u]);
+  }
+  for (; j < m; ++j) step(j, *reinterpret_cast<const float4 *>(Er + (size_t)j * 256));
+#pragma unroll
+  for (int h = 0; h < 4; ++h) *reinterpret_cast<float4 *>(dqp + row * 1024 + h * 256 + lane * 4) = acc[h];
+}
+
+// dk / dv: one workgroup per (32 keys, head, batch); thread = key j0 + (tid & 31) x 8 channels of the head.  The query rows go through
+// LDS in chunks of 32 (dS, P: 32 x 32; q, dO: 32 x 64 of the head).
+constexpr int AB_JT = 32, AB_IC = 32;
+__global__ __launch_bounds__(256) void token_attn_f32_bwd_dkv_kernel(const float *__restrict__ q, int ldq, const float *__restrict__ dout,
+                                                                     const float *__restrict__ P, const float *__restrict__ dS, int n, int m,
+                                                                     float scale, float *__restrict__ dk, float *__restrict__ dv) {
+  __shared__ __attribute__((aligned(16))) float sS[AB_IC][AB_JT], sP[AB_IC][AB_JT], sQ[AB_IC][64 + 4], sG[AB_IC][64 + 4];
+  const int b = blockIdx.z, h = blockIdx.y, j0 = blockIdx.x * AB_JT, tid = threadIdx.x;
+  const int jl = tid & 31, c0 = (tid >> 5) * 8;
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 ak0 = z4, ak1 = z4, av0 = z4, av1 = z4;
+  auto fma4 = [](float s, const float4 &x, float4 &a) {
+    a.x = fmaf(s, x.x, a.x);
+    a.y = fmaf(s, x.y, a.y);
+    a.z = fmaf(s, x.z, a.z);
+    a.w = fmaf(s, x.w, a.w);
+  };
+  const size_t pbase = ((size_t)b * 4 + h) * n * AF_MP + j0;
+  for (int i0 = 0; i0 < n; i0 += AB_IC) {
+    __syncthreads();
+    {
+      const int r = tid >> 3, k4 = (tid & 7) * 4, c8 = (tid & 7) * 8;
+      const bool ok = i0 + r < n;
+      auto ld4 = [&](const float *p) { return ok ? *reinterpret_cast<const float4 *>(p) : make_float4(0.f, 0.f, 0.f, 0.f); };
+      const size_t pi = pbase + (size_t)(i0 + r) * AF_MP + k4;  // j0 + k4 + 3 < AF_MP: the padded width holds every tile
+      *reinterpret_cast<float4 *>(&sS[r][k4]) = ld4(dS + pi);
+      *reinterpret_cast<float4 *>(&sP[r][k4]) = ld4(P + pi);
+      const float *qr = q + ((size_t)b * n + i0 + r) * ldq + h * 64 + c8;
+      const float *gr = dout + ((size_t)b * n + i0 + r) * 256 + h * 64 + c8;
+      *reinterpret_cast<float4 *>(&sQ[r][c8]) = ld4(qr);
+      *reinterpret_cast<float4 *>(&sQ[r][c8 + 4]) = ld4(qr + 4);
+      *reinterpret_cast<float4 *>(&sG[r][c8]) = ld4(gr);
+      *reinterpret_cast<float4 *>(&sG[r][c8 + 4]) = ld4(gr + 4);
+    }
+    __syncthreads();
+    const int ni = min(AB_IC, n - i0);
+    for (int r = 0; r < ni; ++r) {
+      const float s = sS[r][jl], pr = sP[r][jl];
+      fma4(s, *reinterpret_cast<const float4 *>(&sQ[r][c0]), ak0);
+      fma4(s, *reinterpret_cast<const float4 *>(&sQ[r][c0 + 4]), ak1);
+      fma4(pr, *reinterpret_cast<const float4 *>(&sG[r][c0]), av0);
+      fma4(pr, *reinterpret_cast<const float4 *>(&sG[r][c0 + 4]), av1);
+    }
+  }
+  if (j0 + jl >= m) return;
+  float *K = dk + ((size_t)b * m + j0 + jl) * 256 + h * 64 + c0, *Vd = dv + ((size_t)b * m + j0 + jl) * 256 + h * 64 + c0;
+  *reinterpret_cast<float4 *>(K) = make_float4(ak0.x * scale, ak0.y * scale, ak0.z * scale, ak0.w * scale);
+  *reinterpret_cast<float4 *>(K + 4) = make_float4(ak1.x * scale, ak1.y * scale, ak1.z * scale, ak1.w * scale);
+  *reinterpret_cast<float4 *>(Vd) = av0;
+  *reinterpret_cast<float4 *>(Vd + 4) = av1;
 }
 
 // ---- ViT attention (see vit_attn.hip): flash-style; K / V^T chunks in LDS ALREADY SPLIT into bf16 hi / lo planes ---------------
@@ -350,11 +575,54 @@ int unopose_token_attention_f32(const float *q, int ldq, const float *k, int ldk
   hipStream_t s = (hipStream_t)stream;
   if (E)
     hipLaunchKernelGGL(token_attn_f32_kernel<true>, grid, dim3(256), 0, s, q, ldq, k, ldk, vt, qp, ldqp, E, n, m, scale,
-                       out);
+                       out, (float *)nullptr);
   else
     hipLaunchKernelGGL(token_attn_f32_kernel<false>, grid, dim3(256), 0, s, q, ldq, k, ldk, vt, (const float *)nullptr,
-                       0, (const float *)nullptr, n, m, scale, out);
+                       0, (const float *)nullptr, n, m, scale, out, (float *)nullptr);
   return check_launch("token_attention_f32");
+}
+
+int unopose_token_attention_f32_train(const float *q, int ldq, const float *k, int ldk, const float *vt, const float *qp, int ldqp,
+                                      const float *E, int B, int n, int m, float scale, float *out, float *P, unopose_stream_t stream) {
+  UNOPOSE_REQUIRE(q && k && vt && out && P, "token_attention_f32_train: null pointer");
+  UNOPOSE_REQUIRE((qp == nullptr) == (E == nullptr), "token_attention_f32_train: qp and E go together");
+  UNOPOSE_REQUIRE(B >= 0 && n >= 1 && m >= 1 && m <= AF_MP && B <= 65535,
+                  "token_attention_f32_train: m=%d exceeds the %d-key tile", m, AF_MP);
+  UNOPOSE_REQUIRE(ldq >= 256 && ldk >= 256 && ldq % 8 == 0 && ldk % 8 == 0 && (!E || (ldqp >= 1024 && ldqp % 8 == 0)),
+                  "token_attention_f32_train: row strides must be multiples of 8 elements");
+  if (B == 0) return UNOPOSE_OK;
+  dim3 grid(cdiv(n, 16), B);
+  hipStream_t s = (hipStream_t)stream;
+  if (E)
+    hipLaunchKernelGGL((token_attn_f32_kernel<true, true>), grid, dim3(256), 0, s, q, ldq, k, ldk, vt, qp, ldqp, E, n, m, scale, out, P);
+  else
+    hipLaunchKernelGGL((token_attn_f32_kernel<false, true>), grid, dim3(256), 0, s, q, ldq, k, ldk, vt, (const float *)nullptr, 0,
+                       (const float *)nullptr, n, m, scale, out, P);
+  return check_launch("token_attention_f32_train");
+}
+
+int unopose_token_attention_f32_backward(const float *dout, const float *q, int ldq, const float *v, int ldv, const float *kt,
+                                         const float *qp, int ldqp, const float *E, const float *P, int B, int n, int m, float scale,
+                                         float *dS, float *dq, float *dk, float *dv, float *dqp, float *dE, unopose_stream_t stream) {
+  UNOPOSE_REQUIRE(dout && q && v && kt && P && dS && dq && dk && dv, "token_attention_f32_backward: null pointer");
+  UNOPOSE_REQUIRE((qp == nullptr) == (E == nullptr) && (qp == nullptr) == (dqp == nullptr) && (dE == nullptr || E != nullptr),
+                  "token_attention_f32_backward: qp, E and dqp go together (dE only with them)");
+  UNOPOSE_REQUIRE(B >= 0 && n >= 1 && m >= 1 && m <= AF_MP && B <= 65535,
+                  "token_attention_f32_backward: m=%d exceeds the %d-key tile", m, AF_MP);
+  UNOPOSE_REQUIRE(ldq >= 256 && ldv >= 256 && ldq % 8 == 0 && ldv % 8 == 0 && (!qp || (ldqp >= 1024 && ldqp % 8 == 0)),
+                  "token_attention_f32_backward: row strides must be multiples of 8 elements");
+  if (B == 0) return UNOPOSE_OK;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(token_attn_f32_bwd_dq_kernel, dim3(cdiv(n, 16), B), dim3(256), 0, s, dout, v, ldv, P, kt, n, m, scale, dS, dq);
+  int rc = check_launch("token_attention_f32_backward (dq)");
+  if (rc != UNOPOSE_OK) return rc;
+  hipLaunchKernelGGL(token_attn_f32_bwd_dkv_kernel, dim3(cdiv(m, AB_JT), 4, B), dim3(256), 0, s, q, ldq, dout, P, (const float *)dS, n, m,
+                     scale, dk, dv);
+  rc = check_launch("token_attention_f32_backward (dk, dv)");
+  if (rc != UNOPOSE_OK || !qp) return rc;
+  hipLaunchKernelGGL(token_attn_f32_bwd_rpe_kernel, dim3(cdiv(n, 4), B), dim3(256), 0, s, (const float *)dS, qp, ldqp, E, n, m, scale, dqp,
+                     dE);
+  return check_launch("token_attention_f32_backward (rpe)");
 }
 
 int unopose_vit_attention_f32(const float *qkv, int B, int T, int H, float *out, unopose_stream_t stream) {

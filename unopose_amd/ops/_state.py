@@ -42,3 +42,4 @@ TRAIN_OWN_GEMM = True  # False: nn.Linear through the library
 # (round 6 same-box A/B of the training step: 2e10 121-124 ms, 1e10 119-121, 4e9 118.2, 1e9 117-120: scripts/ubench/train_ab.py)
 TRAIN_OWN_GEMM_MIN_FLOP = 4e9
 TRAIN_OWN_GEO = True  # round 6: the geometric embedding under autograd on the table kernels; False: the op-by-op composite
+TRAIN_OWN_ATTN = True  # the token attention core under autograd on csrc/attn_f32.hip (forward + backward kernels); False: the op-by-op composite

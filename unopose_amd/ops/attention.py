@@ -70,18 +70,26 @@ def vit_attention_torch(qkv, heads):
 _KEY_PAD = None
 
 
+def _key_pad():
+    """The kernels' padded key count KP (unopose_token_attention_key_pad())."""
+    global _KEY_PAD
+    if _KEY_PAD is None:
+        _KEY_PAD = lib().unopose_token_attention_key_pad()
+    return _KEY_PAD
+
+
 def token_attention(x, mem, att, heads, embed=None):
     """MultiHeadAttention / RPEMultiHeadAttention core (transformer.py:130-148, 386-405): returns the
     concatenated heads (B,n,C) before the output Linear.  The RPE term q.proj_p(E) is folded:
     q.(W_p e + b_p) = (q W_p).e + q.b_p  (SURVEY.md App-F), so no (B,4,n,m,64) tensor exists.
     Under autocast(bf16) the whole core (q k^T, folded RPE term, softmax, P v) is ONE HIP kernel on the
-    bf16 matrix cores (csrc/attn.hip) that streams E once; in fp32 the op-by-op composite below runs."""
-    global _KEY_PAD
+    bf16 matrix cores (csrc/attn.hip) that streams E once; in fp32 the same scheme with hi/lo-split operands
+    (csrc/attn_f32.hip).  Under autograd (differentiable mode, fp32) the core is `_TokenAttnFn` on the projections'
+    outputs; shapes outside the kernels take the op-by-op composite below."""
+    if st._DIFF and torch.is_grad_enabled() and token_attention_train_ok(x, mem, att, heads, embed):
+        return _token_attention_train(x, mem, att, embed)
     if not st._DIFF and x.is_cuda and heads == 4 and x.shape[-1] == 256:
-        if _KEY_PAD is None:
-            from .._lib import lib
-            _KEY_PAD = lib().unopose_token_attention_key_pad()
-        if mem.shape[1] <= _KEY_PAD:
+        if mem.shape[1] <= _key_pad():
             if torch.is_autocast_enabled():
                 return _token_attention_hip(x, mem, att, embed)
             if x.dtype == torch.float32:
@@ -205,6 +213,79 @@ def _token_attention_hip(x, mem, att, embed):
              ptr(vt), ctypes.c_void_p(q_ptr + C * esz) if rpe else None, yq.stride(1),
              ptr(E) if E is not None else None, B, n, m, 0.125, ptr(out), stream_ptr())
     return out
+
+
+def _transpose_pad_f32(t):
+    """(B,m,256) fp32 rows -> (B,256,KP) channel-major, zero-padded to the kernels' key count (csrc/glue.hip)."""
+    B, m, C = t.shape
+    out = torch.empty(B, C, _key_pad(), dtype=torch.float32, device=t.device)
+    with on_device(t.device):
+        call("unopose_transpose_pad_f32", ptr(t), t.stride(1), B, m, C, _key_pad(), ptr(out), stream_ptr())
+    return out
+
+
+class _TokenAttnFn(torch.autograd.Function):
+    """The attention core of `token_attention_torch` under autograd, from the projections' outputs: q (B,n,256), k / v (B,m,256),
+    RPE: qp (B,n,4,256) = q_h W_p,h (the folded proj_p) and E (B,n,m,256), else None.  Forward = the fp32 eval kernel, which also
+    stores the softmax weights P (B,4,n,KP); backward = csrc/attn_f32.hip's three kernels (dq and dS; dk, dv; dqp and dE with E
+    streamed once).  `bp` (proj_p.bias or None) only receives its gradient: q.b_p is constant along every softmax row, so it
+    changes nothing and its gradient is zero (every trainable parameter still gets one, as DDP expects)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, qp, E, bp):
+        B, n, C = q.shape
+        m = k.shape[1]
+        q, k, v = _c(q), _c(k), _c(v)
+        rpe = qp is not None
+        if rpe:
+            qp, E = _c(qp), _c(E)
+        vt = _transpose_pad_f32(v)
+        out = torch.empty(B, n, C, dtype=torch.float32, device=q.device)
+        P = torch.empty(B, 4, n, _key_pad(), dtype=torch.float32, device=q.device)
+        with on_device(q.device):
+            call("unopose_token_attention_f32_train", ptr(q), C, ptr(k), C, ptr(vt), ptr(qp) if rpe else None, 4 * C,
+                 ptr(E) if rpe else None, B, n, m, 0.125, ptr(out), ptr(P), stream_ptr())
+        ctx.save_for_backward(q, k, v, qp, E, P)
+        ctx.bp_like = None if bp is None else (bp.shape, bp.dtype, bp.device)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, qp, E, P = ctx.saved_tensors
+        B, n, C = q.shape
+        m = k.shape[1]
+        rpe = qp is not None
+        dout = _c(dout.float())
+        kt = _transpose_pad_f32(k)
+        dS = torch.empty_like(P)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        dqp = torch.empty_like(qp) if rpe else None
+        dE = torch.empty_like(E) if rpe and ctx.needs_input_grad[4] else None
+        with on_device(q.device):
+            call("unopose_token_attention_f32_backward", ptr(dout), ptr(q), C, ptr(v), C, ptr(kt), ptr(qp) if rpe else None, 4 * C,
+                 ptr(E) if rpe else None, ptr(P), B, n, m, 0.125, ptr(dS), ptr(dq), ptr(dk), ptr(dv), ptr(dqp) if rpe else None,
+                 ptr(dE) if dE is not None else None, stream_ptr())
+        dbp = None if ctx.bp_like is None else torch.zeros(ctx.bp_like[0], dtype=ctx.bp_like[1], device=ctx.bp_like[2])
+        return dq, dk, dv, dqp, dE, dbp
+
+
+def token_attention_train_ok(x, mem, att, heads, embed=None):
+    """`_TokenAttnFn` applies: switch on, CUDA, fp32 outside autocast, 4 heads x 64, 1 <= m <= KP keys."""
+    f32 = torch.float32
+    return (st.TRAIN_OWN_ATTN and x.is_cuda and heads == 4 and x.shape[-1] == 256 and mem.shape[-1] == 256 and x.shape[1] >= 1
+            and 1 <= mem.shape[1] <= _key_pad() and x.shape[0] <= 65535 and not torch.is_autocast_enabled()
+            and x.dtype == f32 and mem.dtype == f32 and att.proj_q.weight.dtype == f32 and (embed is None or embed.dtype == f32))
+
+
+def _token_attention_train(x, mem, att, embed):
+    """The projections as in the composite (trainable linears, qp = q W_p a torch op: dW_p and its share of dq come from autograd), the
+    core on `_TokenAttnFn`."""
+    B, n, C = x.shape
+    q, k, v = _lin(x, att.proj_q), _lin(mem, att.proj_k), _lin(mem, att.proj_v)
+    if embed is None:
+        return _TokenAttnFn.apply(q, k, v, None, None, None)
+    qp = torch.einsum("bnhc,hcd->bnhd", q.reshape(B, n, 4, 64), att.proj_p.weight.reshape(4, 64, C))
+    return _TokenAttnFn.apply(q, k, v, qp, embed, att.proj_p.bias)
 
 
 def token_attention_torch(x, mem, att, heads, embed=None):
