@@ -141,25 +141,26 @@ int unopose_weighted_procrustes(const float *src, const float *ref,
 int unopose_pe_image_bytes(void);
 int unopose_pe_pack_weights(const float *w1, const float *b1, const float *w2, const float *b2,
                             const float *w3, const float *b3, void *image, unopose_stream_t stream);
-int unopose_pe_group_mlp_max_packed(const float *xyz, int B, int N, float radius, int nsample,
-                                    const void *image, float *out, unopose_stream_t stream);
 
-/* Same with a neighbour-list hand-off between the two scales of PositionalEncoding: a pass may write, per
- * centre, its (padded) neighbour list cand_out (B,N,nsample) int32 and cand_cnt_out (B,N) = number of points
- * inside the radius, or -1 if that exceeded nsample; a later pass over the SAME cloud with a SMALLER radius
- * may read them (cand_in with row stride cand_stride, cand_cnt_in) and test only those candidates instead of
- * scanning all N points.  Results are identical to the full scan.  Any of the pairs may be NULL. */
-int unopose_pe_group_mlp_max_packed_cand(const float *xyz, int B, int N, float radius, int nsample,
-                                         const void *image, const int *cand_in, const int *cand_cnt_in,
-                                         int cand_stride, int *cand_out, int *cand_cnt_out, float *out,
-                                         unopose_stream_t stream);
-/* The same launch with the output placed by the caller: row stride out_ld (in 4-byte units, >= 128; the row of centre (b, j) starts
- * at out + (b N + j) out_ld * 4 bytes) and out_split = 1 writing the 128 channels in the split layout of unopose_linear_f32x3
- * (4 blocks of [hi | lo] bf16) instead of float32 -- both scales of the positional encoding then land side by side in the
- * (B, N, 256)-wide operand of its Conv1d (oneref_predator_fine_point_matching.py:174) without a concatenation or a split pass. */
-int unopose_pe_group_mlp_max_packed_out(const float *xyz, int B, int N, float radius, int nsample, const void *image,
-                                        const int *cand_in, const int *cand_cnt_in, int cand_stride, int *cand_out,
-                                        int *cand_cnt_out, void *out, int out_ld, int out_split, unopose_stream_t stream);
+/* The operator in two launches.  unopose_pe_geometry builds, per centre, the ball-query neighbour list (nsample 16-bit point
+ * ids, the first hits by index, padded with the first: N < 65536), counts = number of points inside the radius or -1 if that
+ * exceeded nsample, and the 3 x 3 local reference frame frames (B,N,9) = [x | y | z axis] -- for one scale, or, with
+ * nsample2 > 0 and radius2 <= radius, for TWO scales of the same cloud in one visit (the second scale's list is the first's
+ * filtered; results equal two separate calls).  cand_in (row stride cand_stride) / cand_cnt_in: optional int32 lists and counts
+ * of an earlier, LARGER-radius pass over the same cloud, tested instead of scanning all N points (same result; a count of -1
+ * scans).  cand_out: optional (B,N,nsample) int32 copy of the first scale's lists.  The grid of the ball query is built once
+ * per workgroup for both scales and the 3 x 3 eigen-solves run one centre per lane.
+ * unopose_pe_mlp_max_packed then runs SharedMLP[6,32,64,128] + max over those lists and frames: row of centre (b, j) at
+ * out + (b N + j) out_ld * 4 bytes (out_ld in 4-byte units, >= 128); out_split = 1 writes the 128 channels in the split layout
+ * of unopose_linear_f32x3 (4 blocks of [hi | lo] bf16) instead of float32, so both scales of the positional encoding land side
+ * by side in the (B, N, 256)-wide operand of its Conv1d (oneref_predator_fine_point_matching.py:174). */
+int unopose_pe_geometry(const float *xyz, int B, int N, float radius, int nsample, float radius2, int nsample2,
+                        const int *cand_in, const int *cand_cnt_in, int cand_stride, void *lists, int *counts,
+                        float *frames, int *cand_out, void *lists2, int *counts2, float *frames2,
+                        unopose_stream_t stream);
+int unopose_pe_mlp_max_packed(const float *xyz, int B, int N, float radius, int nsample, const void *image,
+                              const void *lists, const int *counts, const float *frames, void *out, int out_ld,
+                              int out_split, unopose_stream_t stream);
 
 /* GeometricStructureEmbedding.forward (core/unopose/model/transformer.py:303-350):
  * points (B,n,3) -> out (B,n,n,256), float32 or bfloat16 (out_bf16).  hidden_dim = 256,
@@ -208,7 +209,7 @@ int unopose_geo_embedding_train_backward(const float *points, const int32_t *knn
  * out (B,N,128) float32.  w1 (32,6), w2 (64,32), w3 (128,64) row-major [out][in] with
  * BatchNorm already folded in, b1/b2/b3 the folded biases.  nsample % 32 == 0.
  * Exact fp32 matrix cores (v_mfma_f32_32x32x2_f32); bf16x3 must be 0 (the split-precision form is
- * unopose_pe_group_mlp_max_packed below). */
+ * unopose_pe_geometry + unopose_pe_mlp_max_packed above). */
 int unopose_pe_group_mlp_max(const float *xyz, int B, int N, float radius, int nsample,
                              const float *w1, const float *b1, const float *w2,
                              const float *b2, const float *w3, const float *b3,

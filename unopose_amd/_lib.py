@@ -112,9 +112,8 @@ SIGNATURES = {
     "unopose_linear_f32x3": [_P, _P, _P, _P, _P, ctypes.c_long, _I, _I, _I, _P],
     "unopose_pe_image_bytes": [],
     "unopose_pe_pack_weights": [_P, _P, _P, _P, _P, _P, _P, _P],
-    "unopose_pe_group_mlp_max_packed": [_P, _I, _I, _F, _I, _P, _P, _P],
-    "unopose_pe_group_mlp_max_packed_cand": [_P, _I, _I, _F, _I, _P, _P, _P, _I, _P, _P, _P, _P],
-    "unopose_pe_group_mlp_max_packed_out": [_P, _I, _I, _F, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P],
+    "unopose_pe_geometry": [_P, _I, _I, _F, _I, _F, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "unopose_pe_mlp_max_packed": [_P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _I, _I, _P],
     "unopose_linear_f32x3_bf16": [_P, _P, _P, _P, _P, ctypes.c_long, _I, _I, _P],
     "unopose_pe_group_mlp_max": [_P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     "unopose_geo_embedding": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _F, _F, _I, _I, _I, _P, _P, _P],

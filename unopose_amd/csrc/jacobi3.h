@@ -45,7 +45,8 @@ __device__ __forceinline__ void eig_sym3(float a00, float a01, float a02, float 
 #pragma unroll 1
   for (int sweep = 0; sweep < 6; ++sweep) {
     // converged when the off-diagonal mass is below fp32 resolution of the diagonal (typically after
-    // 3-4 sweeps; every caller evaluates this on wave-uniform data, so the exit is not divergent)
+    // 3-4 sweeps).  Callers with wave-uniform data leave together; pe_geometry_kernel (pe.hip) holds one problem per
+    // lane: the exit diverges and every lane runs exactly its own sweep count
     const float off = a01 * a01 + a02 * a02 + a12 * a12;
     const float dia = a00 * a00 + a11 * a11 + a22 * a22;
     if (off <= 1e-16f * dia) break;

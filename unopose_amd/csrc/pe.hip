@@ -12,6 +12,10 @@
 // are directly the next layer's B operand (the k order inside the contraction is permuted to match the
 // C/D register layout, and the weights are staged in LDS in that permuted order).  Only the (B,N,128)
 // max-pooled result reaches HBM.
+// That is the exact-fp32 kernel (pe_group_mlp_max_kernel).  The bf16 hi/lo-split form further down is two kernels: pe_geometry_kernel writes
+// the lists, counts and frames of one or both scales of a cloud, pe_group_mlp_max_bf16x3_kernel runs the MLP + max over them.
+#include <algorithm>
+
 #include "common.h"
 #include "jacobi3.h"
 
@@ -44,26 +48,26 @@ struct PeGrid {
 };
 __device__ __forceinline__ int pe_cell(float v, float o, float ih, int n) { return max(0, min(n - 1, (int)((v - o) * ih))); }
 
-template <typename NT>
-__device__ __forceinline__ int pe_centre_frame(const float *sx, const float *sy, const float *sz, int N, int S,
-                                               float radius, float r2, int lane, float cx, float cy, float cz,
-                                               NT *nbr, Vec3 &xp, Vec3 &yp, Vec3 &zp, const int *cand = nullptr,
-                                               int ncand = -1, const PeGrid *grid = nullptr) {
+// The ball query alone: fills nbr[0..S) (padding included) and returns the count as described above.  `cand` may be a list in LDS
+// (the wide scale's list of the same centre, CT = u16) or in global memory (CT = int).
+template <typename NT, typename CT>
+__device__ __forceinline__ int pe_ball_query(const float *sx, const float *sy, const float *sz, int N, int S, float r2, int lane,
+                                             float cx, float cy, float cz, NT *nbr, const CT *cand, int ncand, const PeGrid &g, bool use_grid) {
   // ---- ball query (pointnet2 ball_query_gpu.cu:14-49 semantics)
   int cnt = 0, first = 0;
-  if (grid && ncand < 0) {
+  if (use_grid && ncand < 0) {
     const int W = (N + 31) >> 5;
-    for (int w = lane; w < W; w += 64) grid->bits[w] = 0u;
+    for (int w = lane; w < W; w += 64) g.bits[w] = 0u;
     // the nine runs: lane i < 9 looks up run (dy, dz) = (i % 3 - 1, i / 3 - 1)
-    const int icx = pe_cell(cx, grid->ox, grid->ihx, grid->nx), icy = pe_cell(cy, grid->oy, grid->ihy, grid->ny),
-              icz = pe_cell(cz, grid->oz, grid->ihz, grid->nz);
+    const int icx = pe_cell(cx, g.ox, g.ihx, g.nx), icy = pe_cell(cy, g.oy, g.ihy, g.ny),
+              icz = pe_cell(cz, g.oz, g.ihz, g.nz);
     int rs = 0, re = 0;
     if (lane < 9) {
       const int y = icy + lane % 3 - 1, z = icz + lane / 3 - 1;
-      if (y >= 0 && y < grid->ny && z >= 0 && z < grid->nz) {
-        const int row = (z * grid->ny + y) * grid->nx;
-        rs = grid->start[row + max(icx - 1, 0)];
-        re = grid->start[row + min(icx + 1, grid->nx - 1) + 1];
+      if (y >= 0 && y < g.ny && z >= 0 && z < g.nz) {
+        const int row = (z * g.ny + y) * g.nx;
+        rs = g.start[row + max(icx - 1, 0)];
+        re = g.start[row + min(icx + 1, g.nx - 1) + 1];
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -73,10 +77,10 @@ __device__ __forceinline__ int pe_centre_frame(const float *sx, const float *sy,
     for (int i = 0; i < 9; ++i) {
       const int s0 = __builtin_amdgcn_readlane(rs, i), e0 = __builtin_amdgcn_readlane(re, i);
       for (int q = s0 + lane; q < e0; q += 64) {
-        const int k = grid->order[q];
+        const int k = g.order[q];
         const float x = sx[k], y = sy[k], z = sz[k];
         const float d2 = (cx - x) * (cx - x) + (cy - y) * (cy - y) + (cz - z) * (cz - z);
-        if (d2 < r2) atomicOr(&grid->bits[k >> 5], 1u << (k & 31));
+        if (d2 < r2) atomicOr(&g.bits[k >> 5], 1u << (k & 31));
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -85,7 +89,7 @@ __device__ __forceinline__ int pe_centre_frame(const float *sx, const float *sy,
     // the list in index order: lane-owned words, exclusive prefix of their popcounts
     for (int w0 = 0; w0 < W; w0 += 64) {
       const int w = w0 + lane;
-      uint32_t bits = w < W ? grid->bits[w] : 0u;
+      uint32_t bits = w < W ? g.bits[w] : 0u;
       const int pc = __builtin_popcount(bits);
       int incl = pc;
 #pragma unroll
@@ -150,11 +154,18 @@ __device__ __forceinline__ int pe_centre_frame(const float *sx, const float *sy,
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  return cnt;
+}
 
-  // ---- local reference frame (LRF_batch, pointnet2_utils.py:436-481)
-  // (measured and not kept, round 5: the three passes with the padding entries' terms as per-pass constants -- bit-identical, no faster:
-  //  the frame's time is the eigen-solver and the wave reductions, not these reads)
-  float a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0;
+// ---- local reference frame (LRF_batch, pointnet2_utils.py:436-481) in three wave-collective pieces: the covariance of the list,
+// the eigen-solve (eig_sym3: per centre in the fp32 kernel, one centre per LANE in the geometry kernel), the sign vote and x axis.
+// (measured and not kept, round 5: the three passes with the padding entries' terms as per-pass constants -- bit-identical, no faster:
+//  the frame's time is the eigen-solver and the wave reductions, not these reads)
+template <typename NT>
+__device__ __forceinline__ void pe_covariance(const float *sx, const float *sy, const float *sz, int S, int lane, float cx, float cy,
+                                              float cz, const NT *nbr, float &a00, float &a01, float &a02, float &a11, float &a12,
+                                              float &a22) {
+  a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0;
   for (int l = lane; l < S; l += 64) {
     const int k = nbr[l];
     const float x = cx - sx[k], y = cy - sy[k], z = cz - sz[k];
@@ -163,9 +174,12 @@ __device__ __forceinline__ int pe_centre_frame(const float *sx, const float *sy,
   const float inv_s = 1.f / (float)S;
   a00 = wave_sum_f32(a00) * inv_s; a01 = wave_sum_f32(a01) * inv_s; a02 = wave_sum_f32(a02) * inv_s;
   a11 = wave_sum_f32(a11) * inv_s; a12 = wave_sum_f32(a12) * inv_s; a22 = wave_sum_f32(a22) * inv_s;
-  Vec3 e0, e1, z0;
-  float l0, l1, l2;
-  eig_sym3(a00, a01, a02, a11, a12, a22, e0, e1, z0, l0, l1, l2);
+}
+
+// z0: the eigenvector of the smallest eigenvalue of the covariance (wave-uniform)
+template <typename NT>
+__device__ __forceinline__ void pe_frame_axes(const float *sx, const float *sy, const float *sz, int S, float radius, int lane,
+                                              float cx, float cy, float cz, const NT *nbr, Vec3 z0, Vec3 &xp, Vec3 &yp, Vec3 &zp) {
   int vote = 0;
   for (int l0i = 0; l0i < S; l0i += 64) {
     const int l = l0i + lane;
@@ -192,6 +206,20 @@ __device__ __forceinline__ int pe_centre_frame(const float *sx, const float *sy,
   const float nacc = sqrtf(vx * vx + vy * vy + vz * vz) + 1e-10f;
   xp = v3(vx / nacc, vy / nacc, vz / nacc);
   yp = cross(xp, zp);
+}
+
+// Ball query + frame of one centre, the eigen-solve on wave-uniform data (the exact-fp32 kernel below).
+template <typename NT>
+__device__ __forceinline__ int pe_centre_frame(const float *sx, const float *sy, const float *sz, int N, int S,
+                                               float radius, float r2, int lane, float cx, float cy, float cz,
+                                               NT *nbr, Vec3 &xp, Vec3 &yp, Vec3 &zp) {
+  const int cnt = pe_ball_query<NT, int>(sx, sy, sz, N, S, r2, lane, cx, cy, cz, nbr, nullptr, -1, PeGrid{}, false);
+  float a00, a01, a02, a11, a12, a22;
+  pe_covariance(sx, sy, sz, S, lane, cx, cy, cz, nbr, a00, a01, a02, a11, a12, a22);
+  Vec3 e0, e1, z0;
+  float l0, l1, l2;
+  eig_sym3(a00, a01, a02, a11, a12, a22, e0, e1, z0, l0, l1, l2);
+  pe_frame_axes(sx, sy, sz, S, radius, lane, cx, cy, cz, nbr, z0, xp, yp, zp);
   return cnt;
 }
 
@@ -370,43 +398,55 @@ __global__ __launch_bounds__(256) void pe_pack_weights_kernel(const float *__res
   if (tid < 128) L->b3[tid] = b3[tid];
 }
 
-constexpr int PE_NW = 4;  // waves per workgroup of the bf16x3 kernel: two 4-wave workgroups per CU; 8 = one per CU (measured 4 % slower)
-__global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3_kernel(
-    const float *__restrict__ xyz, int N, float radius, int S, int cpw, const uint4 *__restrict__ image,
-    const int *__restrict__ cand_in, const int *__restrict__ cand_cnt_in, int cand_stride, int *__restrict__ cand_out,
-    int *__restrict__ cand_cnt_out, float *__restrict__ out, int out_ld, int out_split, int use_grid) {
+// ------------------------------------------------------------------------------------------------
+// The geometry of the bf16x3 path in a kernel of its own: neighbour lists, counts and frames of every centre, for ONE scale or for
+// the TWO scales of the positional encoding in one visit (the narrow scale's list is the wide one's filtered, exactly as the
+// cand_in hand-off).  No weight image in LDS and eight waves per workgroup: the VALU- and latency-bound ball query / list / frame passes run
+// at up to six waves per SIMD instead of the MLP kernel's two, and the cloud's grid is built once per workgroup for both scales.
+// The 3 x 3 eigen-solve is the one piece that is NOT wave-collective any more: a wave first builds the lists and covariances of a
+// batch of PE_GB of its centres (lists kept in LDS), lane i keeping centre i's wide-scale matrix and lane PE_GB + i its narrow-scale
+// one, calls eig_sym3 ONCE with per-lane data (every lane runs exactly its own sweep count; lanes without a problem hold the zero
+// matrix and leave at the first test), and then finishes the batch's frames with the wave-collective vote / x-axis passes.  The
+// operations of every problem are those of the fused kernel; only who executes them changed.
+constexpr int PE_GW = 8;  // waves per workgroup
+constexpr int PE_GB = 4;  // centres per eigen-solve batch of a wave (measured at 32 x 2048, both scales: 4 centres per wave in one batch 171 us,
+                          // 8 per wave in batches of 4 / 8: 179 / 183 us, 16 per wave in batches of 8: 189 us -- shorter waves balance better)
+constexpr int PE_GEOM_SCRATCH = PE_GCELLS + 6 * PE_GW + PE_GW;  // 4-byte words of the grid build's scratch
+
+__device__ __forceinline__ float pe_readlane_f32(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+__global__ __launch_bounds__(PE_GW * 64) void pe_geometry_kernel(
+    const float *__restrict__ xyz, int N, int cpw, float rad0, int S0, float rad1, int S1, const int *__restrict__ cand_in,
+    const int *__restrict__ cand_cnt_in, int cand_stride, u16 *__restrict__ lists0, int *__restrict__ cnt0,
+    float *__restrict__ frames0, int *__restrict__ cand_out, u16 *__restrict__ lists1, int *__restrict__ cnt1,
+    float *__restrict__ frames1, int use_grid) {
   extern __shared__ float4 smem4[];
-  PeLdsB *L = reinterpret_cast<PeLdsB *>(smem4);
-  float *sx = reinterpret_cast<float *>(L + 1);
+  float *sx = reinterpret_cast<float *>(smem4);
   float *sy = sx + N, *sz = sy + N;
-  float *stage_all = sz + N;                                           // [PE_NW][128] floats; the grid build's counters and each wave's bit map live here too
-  u16 *nbr_all = reinterpret_cast<u16 *>(stage_all + PE_NW * 128);    // [PE_NW][S] neighbour lists (N < 65536)
-  u16 *gstart = nbr_all + PE_NW * S;                                   // grid (use_grid): [PE_GCELLS + 2] cell starts, then [N] point ids by cell
+  const int BW = use_grid ? (N + 31) >> 5 : 0;                 // words of a wave's bit map
+  uint32_t *bits_all = reinterpret_cast<uint32_t *>(sz + N);  // [PE_GW][BW] bit maps
+  u16 *lists_all = reinterpret_cast<u16 *>(bits_all + PE_GW * BW);  // [PE_GW][PE_GB][S0 + S1] neighbour lists of a batch
+  // the grid build's scratch borrows the lists' area (the host sizes it for both): cell counters / fill cursors, partial extrema, wave totals
+  uint32_t *cnt32 = reinterpret_cast<uint32_t *>(lists_all);  // [PE_GCELLS]
+  float *red = reinterpret_cast<float *>(cnt32 + PE_GCELLS);  // [6 PE_GW]
+  uint32_t *wtot = reinterpret_cast<uint32_t *>(red + 6 * PE_GW);  // [PE_GW]
+  const int SS = S0 + S1;
+  u16 *gstart = lists_all + max(PE_GW * PE_GB * SS, 2 * PE_GEOM_SCRATCH);  // grid (use_grid): [PE_GCELLS + 2] cell starts, then [N] point ids by cell
   u16 *gorder = gstart + PE_GCELLS + 2;
-  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int half = lane >> 5, col = lane & 31;
-  u16 *nbr = nbr_all + wave * S;
-  float *stage = stage_all + wave * 128;
+  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const float *P = xyz + (size_t)b * N * 3;
 
-  for (int e = tid; e < N * 3; e += PE_NW * 64) {
+  for (int e = tid; e < N * 3; e += PE_GW * 64) {
     const float v = P[e];
     const int p = e / 3, comp = e - p * 3;
     (comp == 0 ? sx : comp == 1 ? sy : sz)[p] = v;
   }
-  // the LDS weight image (hi/lo bf16, permuted, swizzled; built once by pe_pack_weights_kernel) is copied
-  // verbatim with coalesced 16-byte loads
-  for (int e = tid; e < (int)(sizeof(PeLdsB) / 16); e += PE_NW * 64) smem4[e] = *reinterpret_cast<const float4 *>(image + e);
   __syncthreads();
-  const float r2 = radius * radius;
-  PeGrid grid;
+  PeGrid grid = {};
   if (use_grid) {
-    // ---- the cloud's grid, built by every workgroup for itself (2 k points: a few microseconds against ~150 of centres)
-    static_assert(PE_NW * 128 >= PE_GCELLS, "the cell counters borrow the staging area");
-    uint32_t *cnt32 = reinterpret_cast<uint32_t *>(stage_all);
-    float *red = reinterpret_cast<float *>(nbr_all);  // 6 x PE_NW partial extrema (the lists are not in use yet)
+    // ---- the cloud's grid (cells of the WIDE radius serve both scales: a cell edge only has to be >= the radius queried)
     float lo[3] = {3e38f, 3e38f, 3e38f}, hi[3] = {-3e38f, -3e38f, -3e38f};
-    for (int p = tid; p < N; p += PE_NW * 64) {
+    for (int p = tid; p < N; p += PE_GW * 64) {
       lo[0] = fminf(lo[0], sx[p]), hi[0] = fmaxf(hi[0], sx[p]);
       lo[1] = fminf(lo[1], sy[p]), hi[1] = fmaxf(hi[1], sy[p]);
       lo[2] = fminf(lo[2], sz[p]), hi[2] = fmaxf(hi[2], sz[p]);
@@ -417,15 +457,15 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
       hi[a] = wave_max_f32(hi[a]);
       if (lane == 0) red[wave * 6 + a] = lo[a], red[wave * 6 + 3 + a] = hi[a];
     }
-    for (int c = tid; c < PE_GCELLS; c += PE_NW * 64) cnt32[c] = 0u;
+    for (int c = tid; c < PE_GCELLS; c += PE_GW * 64) cnt32[c] = 0u;
     __syncthreads();
     float org[3], ih[3];
     int nd[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       float l = red[a], h = red[3 + a];
-      for (int w = 1; w < PE_NW; ++w) l = fminf(l, red[w * 6 + a]), h = fmaxf(h, red[w * 6 + 3 + a]);
-      const float ext = h - l, h0 = radius * 1.001f;  // (cells a little wider than the radius: a neighbour is at most ONE cell away under fp rounding)
+      for (int w = 1; w < PE_GW; ++w) l = fminf(l, red[w * 6 + a]), h = fmaxf(h, red[w * 6 + 3 + a]);
+      const float ext = h - l, h0 = rad0 * 1.001f;  // (cells a little wider than the radius: a neighbour is at most ONE cell away under fp rounding)
       int n = (int)(ext / h0) + 1;
       float edge = h0;
       if (!(n <= PE_GDIM)) n = PE_GDIM, edge = fmaxf(h0, ext / (float)PE_GDIM * 1.001f);
@@ -436,62 +476,167 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
     }
     grid.ox = org[0], grid.oy = org[1], grid.oz = org[2], grid.ihx = ih[0], grid.ihy = ih[1], grid.ihz = ih[2];
     grid.nx = nd[0], grid.ny = nd[1], grid.nz = nd[2];
-    grid.start = gstart, grid.order = gorder, grid.bits = reinterpret_cast<uint32_t *>(stage);
+    grid.start = gstart, grid.order = gorder, grid.bits = bits_all + wave * BW;
     auto cell_of = [&](int p) {
       return (pe_cell(sz[p], grid.oz, grid.ihz, grid.nz) * grid.ny + pe_cell(sy[p], grid.oy, grid.ihy, grid.ny)) * grid.nx +
              pe_cell(sx[p], grid.ox, grid.ihx, grid.nx);
     };
-    for (int p = tid; p < N; p += PE_NW * 64) atomicAdd(&cnt32[cell_of(p)], 1u);
+    for (int p = tid; p < N; p += PE_GW * 64) atomicAdd(&cnt32[cell_of(p)], 1u);
     __syncthreads();
-    {  // exclusive scan of the PE_GCELLS counters: PE_GCELLS / (PE_NW * 64) consecutive cells per thread, wave scan, wave totals through LDS
-      constexpr int CPT = PE_GCELLS / (PE_NW * 64);
-      static_assert(CPT * PE_NW * 64 == PE_GCELLS, "cells divide among the threads");
-      uint32_t c[CPT], sum = 0;
-#pragma unroll
-      for (int e = 0; e < CPT; ++e) c[e] = cnt32[tid * CPT + e], sum += c[e];
-      uint32_t incl = sum;
+    {  // exclusive scan of the PE_GCELLS counters: one cell per thread (of the first PE_GCELLS), wave scan, wave totals through LDS
+      static_assert(PE_GW * 64 >= PE_GCELLS && PE_GCELLS % 64 == 0, "one cell per thread");
+      const uint32_t c = tid < PE_GCELLS ? cnt32[tid] : 0u;
+      uint32_t incl = c;
 #pragma unroll
       for (int d = 1; d < 64; d <<= 1) {
         const uint32_t t = __shfl_up(incl, d);
         if (lane >= d) incl += t;
       }
-      uint32_t *wtot = reinterpret_cast<uint32_t *>(red) + 32;
       if (lane == 63) wtot[wave] = incl;
       __syncthreads();
-      uint32_t base = incl - sum;
-      for (int w = 0; w < wave; ++w) base += wtot[w];
-#pragma unroll
-      for (int e = 0; e < CPT; ++e) {
-        gstart[tid * CPT + e] = (u16)base;
-        cnt32[tid * CPT + e] = base;  // the fill pass's cursor
-        base += c[e];
+      if (tid < PE_GCELLS) {
+        uint32_t base = incl - c;
+        for (int w = 0; w < wave; ++w) base += wtot[w];
+        gstart[tid] = (u16)base;
+        cnt32[tid] = base;  // the fill pass's cursor
+        if (tid == PE_GCELLS - 1) gstart[PE_GCELLS] = (u16)(base + c);
       }
-      if (tid == PE_NW * 64 - 1) gstart[PE_GCELLS] = (u16)base;
     }
     __syncthreads();
-    for (int p = tid; p < N; p += PE_NW * 64) gorder[atomicAdd(&cnt32[cell_of(p)], 1u)] = (u16)p;
+    for (int p = tid; p < N; p += PE_GW * 64) gorder[atomicAdd(&cnt32[cell_of(p)], 1u)] = (u16)p;
     __syncthreads();
   }
+  const float r2_0 = rad0 * rad0, r2_1 = rad1 * rad1;
+  u16 *mylists = lists_all + wave * PE_GB * SS;
+  const int jbase = (blockIdx.x * PE_GW + wave) * cpw;
+
+  for (int c0 = 0; c0 < cpw; c0 += PE_GB) {
+    if (jbase + c0 >= N) break;  // wave-uniform
+    const int nb = min(PE_GB, min(cpw - c0, N - jbase - c0));  // centres of this batch
+    float m00 = 0.f, m01 = 0.f, m02 = 0.f, m11 = 0.f, m12 = 0.f, m22 = 0.f;  // this LANE's eigen-problem
+#pragma unroll 1
+    for (int i = 0; i < nb; ++i) {
+      const int j = jbase + c0 + i;
+      const size_t row = (size_t)b * N + j;
+      const float cx = sx[j], cy = sy[j], cz = sz[j];
+      u16 *n0 = mylists + i * SS, *n1 = n0 + S0;
+      const int *cand = nullptr;
+      int ncand = -1;
+      if (cand_in) {
+        ncand = cand_cnt_in[row];  // -1: the producer's list overflowed, scan everything
+        cand = cand_in + row * cand_stride;
+      }
+      const int c = pe_ball_query<u16, int>(sx, sy, sz, N, S0, r2_0, lane, cx, cy, cz, n0, cand, ncand, grid, use_grid != 0);
+      {
+        uint32_t *dst = reinterpret_cast<uint32_t *>(lists0 + row * S0);
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(n0);
+        for (int l = lane; l < (S0 >> 1); l += 64) dst[l] = src[l];
+        if (cand_out) {
+          int *co = cand_out + row * S0;
+          for (int l = lane; l < S0; l += 64) co[l] = n0[l];
+        }
+        if (lane == 0) cnt0[row] = c <= S0 ? c : -1;
+      }
+      float a00, a01, a02, a11, a12, a22;
+      pe_covariance(sx, sy, sz, S0, lane, cx, cy, cz, n0, a00, a01, a02, a11, a12, a22);
+      if (lane == i) m00 = a00, m01 = a01, m02 = a02, m11 = a11, m12 = a12, m22 = a22;
+      if (S1) {
+        // the narrow scale tests the wide list's points (all of them lie in it) unless that list overflowed
+        const int c1 = pe_ball_query<u16, u16>(sx, sy, sz, N, S1, r2_1, lane, cx, cy, cz, n1, n0, c <= S0 ? c : -1, grid, use_grid != 0);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(lists1 + row * S1);
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(n1);
+        for (int l = lane; l < (S1 >> 1); l += 64) dst[l] = src[l];
+        if (lane == 0) cnt1[row] = c1 <= S1 ? c1 : -1;
+        pe_covariance(sx, sy, sz, S1, lane, cx, cy, cz, n1, a00, a01, a02, a11, a12, a22);
+        if (lane == PE_GB + i) m00 = a00, m01 = a01, m02 = a02, m11 = a11, m12 = a12, m22 = a22;
+      }
+    }
+    Vec3 e0, e1, z0;
+    float l0, l1, l2;
+    eig_sym3(m00, m01, m02, m11, m12, m22, e0, e1, z0, l0, l1, l2);
+#pragma unroll 1
+    for (int i = 0; i < nb; ++i) {
+      const int j = jbase + c0 + i;
+      const size_t row = (size_t)b * N + j;
+      const float cx = sx[j], cy = sy[j], cz = sz[j];
+      const u16 *n0 = mylists + i * SS, *n1 = n0 + S0;
+#pragma unroll 1
+      for (int sc = 0; sc < (S1 ? 2 : 1); ++sc) {
+        const int src_lane = sc ? PE_GB + i : i;
+        const Vec3 z = v3(pe_readlane_f32(z0.x, src_lane), pe_readlane_f32(z0.y, src_lane), pe_readlane_f32(z0.z, src_lane));
+        Vec3 xp, yp, zp;
+        pe_frame_axes(sx, sy, sz, sc ? S1 : S0, sc ? rad1 : rad0, lane, cx, cy, cz, sc ? n1 : n0, z, xp, yp, zp);
+        const float f = lane == 0 ? xp.x : lane == 1 ? xp.y : lane == 2 ? xp.z : lane == 3 ? yp.x : lane == 4 ? yp.y : lane == 5 ? yp.z
+                        : lane == 6 ? zp.x : lane == 7 ? zp.y : zp.z;
+        if (lane < 9) (sc ? frames1 : frames0)[row * 9 + lane] = f;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// The MLP of the bf16x3 path: list, count and frame of every centre come from pe_geometry_kernel; the tile loop is the fused
+// kernel's.  A centre's list (S 16-bit ids), frame and count are fetched into registers one centre ahead, under the previous
+// centre's tiles.
+constexpr int PE_NW = 4;  // waves per workgroup of the bf16x3 kernel: two 4-wave workgroups per CU; 8 = one per CU (measured 4 % slower)
+__global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3_kernel(
+    const float *__restrict__ xyz, int N, float radius, int S, int cpw, const uint4 *__restrict__ image,
+    const u16 *__restrict__ lists, const int *__restrict__ counts, const float *__restrict__ frames, float *__restrict__ out,
+    int out_ld, int out_split) {
+  extern __shared__ float4 smem4[];
+  PeLdsB *L = reinterpret_cast<PeLdsB *>(smem4);
+  float *sx = reinterpret_cast<float *>(L + 1);
+  float *sy = sx + N, *sz = sy + N;
+  float *stage_all = sz + N;                                           // [PE_NW][128] floats
+  u16 *nbr_all = reinterpret_cast<u16 *>(stage_all + PE_NW * 128);    // [PE_NW][S] neighbour lists (N < 65536)
+  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int half = lane >> 5, col = lane & 31;
+  u16 *nbr = nbr_all + wave * S;
+  float *stage = stage_all + wave * 128;
+  const float *P = xyz + (size_t)b * N * 3;
+  const int SW = S >> 1;  // list length in 4-byte words
+  const uint32_t *LW = reinterpret_cast<const uint32_t *>(lists) + (size_t)b * N * SW;
+  uint32_t pw0 = 0u, pw1 = 0u;  // the next centre's list words lane, lane + 64
+  float pf = 0.f;               // lanes 0..8: its frame; lane 9: its count
+  auto fetch = [&](int j) {
+    const uint32_t *p = LW + (size_t)j * SW;
+    pw0 = lane < SW ? p[lane] : 0u;
+    pw1 = lane + 64 < SW ? p[lane + 64] : 0u;
+    const size_t row = (size_t)b * N + j;
+    pf = lane < 9 ? frames[row * 9 + lane] : lane == 9 ? __int_as_float(counts[row]) : 0.f;
+  };
+  const int j0 = (blockIdx.x * PE_NW + wave) * cpw;
+  if (j0 < N) fetch(j0);
+
+  for (int e = tid; e < N * 3; e += PE_NW * 64) {
+    const float v = P[e];
+    const int p = e / 3, comp = e - p * 3;
+    (comp == 0 ? sx : comp == 1 ? sy : sz)[p] = v;
+  }
+  // the LDS weight image (hi/lo bf16, permuted, swizzled; built once by pe_pack_weights_kernel) is copied
+  // verbatim with coalesced 16-byte loads
+  for (int e = tid; e < (int)(sizeof(PeLdsB) / 16); e += PE_NW * 64) smem4[e] = *reinterpret_cast<const float4 *>(image + e);
+  __syncthreads();
 
   for (int ci = 0; ci < cpw; ++ci) {
-    const int j = (blockIdx.x * PE_NW + wave) * cpw + ci;
+    const int j = j0 + ci;
     if (j >= N) break;  // wave-uniform
     const float cx = sx[j], cy = sy[j], cz = sz[j];
-    Vec3 xp, yp, zp;
-    // The larger-radius pass of a cloud hands its neighbour list to the smaller-radius pass: that one then
-    // tests <= S_large candidates instead of scanning all N points (the full scan is ~1/3 of a small-S launch).
-    const int *cand = nullptr;
-    int ncand = -1;
-    if (cand_in) {
-      ncand = cand_cnt_in[(size_t)b * N + j];  // -1: the producer's list overflowed, scan everything
-      cand = cand_in + ((size_t)b * N + j) * cand_stride;
+    {
+      uint32_t *nw = reinterpret_cast<uint32_t *>(nbr);
+      if (lane < SW) nw[lane] = pw0;
+      if (lane + 64 < SW) nw[lane + 64] = pw1;
+      for (int l = lane + 128; l < SW; l += 64) nw[l] = LW[(size_t)j * SW + l];  // (lists longer than 256: not fetched ahead)
     }
-    const int cnt = pe_centre_frame(sx, sy, sz, N, S, radius, r2, lane, cx, cy, cz, nbr, xp, yp, zp, cand, ncand, use_grid ? &grid : nullptr);
-    if (cand_out) {
-      int *co = cand_out + ((size_t)b * N + j) * S;
-      for (int l = lane; l < S; l += 64) co[l] = nbr[l];
-      if (lane == 0) cand_cnt_out[(size_t)b * N + j] = cnt <= S ? cnt : -1;
-    }
+    const Vec3 xp = v3(pe_readlane_f32(pf, 0), pe_readlane_f32(pf, 1), pe_readlane_f32(pf, 2));
+    const Vec3 yp = v3(pe_readlane_f32(pf, 3), pe_readlane_f32(pf, 4), pe_readlane_f32(pf, 5));
+    const Vec3 zp = v3(pe_readlane_f32(pf, 6), pe_readlane_f32(pf, 7), pe_readlane_f32(pf, 8));
+    const int cnt_in = __builtin_amdgcn_readlane(__float_as_int(pf), 9);
+    const int cnt = cnt_in < 0 ? S + 1 : cnt_in;  // -1: more points inside the radius than the list holds
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (ci + 1 < cpw && j + 1 < N) fetch(j + 1);
 
     f32x16 rmax[4];
 #pragma unroll
@@ -661,46 +806,57 @@ int unopose_pe_pack_weights(const float *w1, const float *b1, const float *w2, c
   return check_launch("pe_pack_weights");
 }
 
-int unopose_pe_group_mlp_max_packed(const float *xyz, int B, int N, float radius, int nsample, const void *image,
-                                    float *out, unopose_stream_t stream) {
-  return unopose_pe_group_mlp_max_packed_cand(xyz, B, N, radius, nsample, image, nullptr, nullptr, 0, nullptr, nullptr,
-                                              out, stream);
-}
-
-int unopose_pe_group_mlp_max_packed_cand(const float *xyz, int B, int N, float radius, int nsample, const void *image,
-                                         const int *cand_in, const int *cand_cnt_in, int cand_stride, int *cand_out,
-                                         int *cand_cnt_out, float *out, unopose_stream_t stream) {
-  return unopose_pe_group_mlp_max_packed_out(xyz, B, N, radius, nsample, image, cand_in, cand_cnt_in, cand_stride, cand_out,
-                                             cand_cnt_out, out, 128, 0, stream);
-}
-
-int unopose_pe_group_mlp_max_packed_out(const float *xyz, int B, int N, float radius, int nsample, const void *image,
-                                        const int *cand_in, const int *cand_cnt_in, int cand_stride, int *cand_out,
-                                        int *cand_cnt_out, void *out, int out_ld, int out_split, unopose_stream_t stream) {
-  UNOPOSE_REQUIRE(xyz && image && out, "pe_group_mlp_max_packed: null pointer");
-  UNOPOSE_REQUIRE(out_ld >= 128 && (out_split == 0 || out_split == 1), "pe_group_mlp_max_packed: bad output stride / mode");
-  UNOPOSE_REQUIRE((cand_in == nullptr) == (cand_cnt_in == nullptr) && (cand_out == nullptr) == (cand_cnt_out == nullptr) &&
-                      (!cand_in || cand_stride >= 1),
-                  "pe_group_mlp_max_packed: candidate list and its counts go together");
-  UNOPOSE_REQUIRE(B >= 0 && N >= 1 && nsample >= 32 && nsample % 32 == 0 && B <= 65535,
-                  "pe_group_mlp_max_packed: nsample must be a positive multiple of 32 (got %d)", nsample);
+int unopose_pe_geometry(const float *xyz, int B, int N, float radius, int nsample, float radius2, int nsample2,
+                        const int *cand_in, const int *cand_cnt_in, int cand_stride, void *lists, int *counts, float *frames,
+                        int *cand_out, void *lists2, int *counts2, float *frames2, unopose_stream_t stream) {
+  UNOPOSE_REQUIRE(xyz && lists && counts && frames, "pe_geometry: null pointer");
+  UNOPOSE_REQUIRE((cand_in == nullptr) == (cand_cnt_in == nullptr) && (!cand_in || cand_stride >= 1),
+                  "pe_geometry: candidate list and its counts go together");
+  UNOPOSE_REQUIRE(B >= 0 && N >= 1 && nsample >= 32 && nsample % 32 == 0 && nsample2 >= 0 && nsample2 % 32 == 0 && B <= 65535,
+                  "pe_geometry: nsample must be a positive multiple of 32 (got %d, %d)", nsample, nsample2);
+  UNOPOSE_REQUIRE(nsample2 == 0 || (lists2 && counts2 && frames2 && radius2 <= radius),
+                  "pe_geometry: the second scale needs its outputs and a radius no larger than the first's");
   if (B == 0) return UNOPOSE_OK;
-  // cloud (3 N floats) + staging + 16-bit neighbour lists; the ball query's grid (cell starts + the cell-sorted point ids) when the
-  // cloud's bit map fits a wave's staging row and the whole still leaves room for two workgroups per CU or the cloud is large anyway
-  size_t lds = sizeof(PeLdsB) + ((size_t)3 * N + PE_NW * 128) * 4 + (size_t)PE_NW * nsample * 2;
-  UNOPOSE_REQUIRE(N < 65536 && lds <= 160 * 1024, "pe_group_mlp_max_packed: N=%d nsample=%d exceed the LDS tile", N, nsample);
-  const size_t grid_bytes = ((size_t)PE_GCELLS + 2 + (size_t)N) * 2;
-  const int use_grid = radius > 0.f && N <= 4096 && N >= 256 && lds + grid_bytes <= 160 * 1024 && (lds + grid_bytes <= 80 * 1024 || lds > 80 * 1024);
+  // cloud (3 N floats) + the 16-bit lists of a batch (the grid build's scratch borrows their area); with the ball query's grid, the
+  // waves' bit maps and the grid itself (cell starts + the cell-sorted point ids).  The grid takes clouds of 256..4096 points.
+  const size_t lists_bytes = (size_t)2 * std::max(PE_GW * PE_GB * (nsample + nsample2), 2 * PE_GEOM_SCRATCH);
+  size_t lds = (size_t)3 * N * 4 + lists_bytes;
+  const size_t grid_bytes = ((size_t)PE_GCELLS + 2 + (size_t)N) * 2 + (size_t)PE_GW * ((N + 31) >> 5) * 4;
+  UNOPOSE_REQUIRE(N < 65536 && lds <= 160 * 1024, "pe_geometry: N=%d nsample=%d+%d exceed the LDS tile", N, nsample, nsample2);
+  const int use_grid = radius > 0.f && N <= 4096 && N >= 256 && lds + grid_bytes <= 160 * 1024;
   if (use_grid) lds += grid_bytes;
   lds = (lds + 15) & ~(size_t)15;
   static bool opt[64];
-  if (lds_optin(opt, (const void *)pe_group_mlp_max_bf16x3_kernel, 160 * 1024, "pe_group_mlp_max_packed") != UNOPOSE_OK) return UNOPOSE_ELAUNCH;
+  if (lds_optin(opt, (const void *)pe_geometry_kernel, 160 * 1024, "pe_geometry") != UNOPOSE_OK) return UNOPOSE_ELAUNCH;
+  const long centres = (long)B * N;
+  const int cpw = centres >= 16384 ? PE_GB : centres >= 8192 ? 2 : 1;
+  dim3 grid(cdiv(N, PE_GW * cpw), B);
+  hipLaunchKernelGGL(pe_geometry_kernel, grid, dim3(PE_GW * 64), lds, (hipStream_t)stream, xyz, N, cpw, radius, nsample, radius2,
+                     nsample2, cand_in, cand_cnt_in, cand_stride, (u16 *)lists, counts, frames, cand_out, (u16 *)lists2, counts2,
+                     frames2, use_grid);
+  return check_launch("pe_geometry");
+}
+
+int unopose_pe_mlp_max_packed(const float *xyz, int B, int N, float radius, int nsample, const void *image, const void *lists,
+                              const int *counts, const float *frames, void *out, int out_ld, int out_split,
+                              unopose_stream_t stream) {
+  UNOPOSE_REQUIRE(xyz && image && lists && counts && frames && out, "pe_mlp_max_packed: null pointer");
+  UNOPOSE_REQUIRE(out_ld >= 128 && (out_split == 0 || out_split == 1), "pe_mlp_max_packed: bad output stride / mode");
+  UNOPOSE_REQUIRE(B >= 0 && N >= 1 && nsample >= 32 && nsample % 32 == 0 && B <= 65535,
+                  "pe_mlp_max_packed: nsample must be a positive multiple of 32 (got %d)", nsample);
+  if (B == 0) return UNOPOSE_OK;
+  // weight image + cloud (3 N floats) + staging + 16-bit neighbour lists
+  size_t lds = sizeof(PeLdsB) + ((size_t)3 * N + PE_NW * 128) * 4 + (size_t)PE_NW * nsample * 2;
+  UNOPOSE_REQUIRE(N < 65536 && lds <= 160 * 1024, "pe_mlp_max_packed: N=%d nsample=%d exceed the LDS tile", N, nsample);
+  lds = (lds + 15) & ~(size_t)15;
+  static bool opt[64];
+  if (lds_optin(opt, (const void *)pe_group_mlp_max_bf16x3_kernel, 160 * 1024, "pe_mlp_max_packed") != UNOPOSE_OK) return UNOPOSE_ELAUNCH;
   const long centres = (long)B * N;
   const int cpw = centres >= 65536 ? 16 : centres >= 32768 ? 8 : centres >= 8192 ? 4 : centres >= 2048 ? 2 : 1;
   dim3 grid(cdiv(N, PE_NW * cpw), B);
   hipLaunchKernelGGL(pe_group_mlp_max_bf16x3_kernel, grid, dim3(PE_NW * 64), lds, (hipStream_t)stream, xyz, N, radius, nsample,
-                     cpw, (const uint4 *)image, cand_in, cand_cnt_in, cand_stride, cand_out, cand_cnt_out, (float *)out, out_ld, out_split, use_grid);
-  return check_launch("pe_group_mlp_max_packed");
+                     cpw, (const uint4 *)image, (const u16 *)lists, counts, frames, (float *)out, out_ld, out_split);
+  return check_launch("pe_mlp_max_packed");
 }
 
 int unopose_pe_group_mlp_max(const float *xyz, int B, int N, float radius, int nsample, const float *w1,
@@ -718,7 +874,7 @@ int unopose_pe_group_mlp_max(const float *xyz, int B, int N, float radius, int n
   const int cpw = centres >= 32768 ? 8 : centres >= 8192 ? 4 : centres >= 2048 ? 2 : 1;
   dim3 grid(cdiv(N, 4 * cpw), B);
   UNOPOSE_REQUIRE(!bf16x3, "pe_group_mlp_max: the bf16x3 form takes a packed weight image "
-                           "(unopose_pe_pack_weights + unopose_pe_group_mlp_max_packed)");
+                           "(unopose_pe_pack_weights + unopose_pe_geometry + unopose_pe_mlp_max_packed)");
   hipLaunchKernelGGL(pe_group_mlp_max_kernel, grid, dim3(256), lds, (hipStream_t)stream, xyz, N, radius, nsample, cpw,
                      w1, b1, w2, b2, w3, b3, out);
   return check_launch("pe_group_mlp_max");

@@ -608,8 +608,8 @@ class PositionalEncoding(nn.Module):
         self.mlp3 = _Conv1d(256, out_dim)
 
     def groups(self, pts):
-        """Both scales' grouped features, max-pooled: (B,N,3) -> (B,N,256) fp32 = [scale 1 | scale 2].  Only the two
-        fused HIP launches (no library GEMM, no inter-workgroup waits), so it may run on a side stream."""
+        """Both scales' grouped features, max-pooled: (B,N,3) -> (B,N,256) fp32 = [scale 1 | scale 2].  Only the PE's own
+        HIP launches (no library GEMM, no inter-workgroup waits), so it may run on a side stream."""
         pts = pts.float()
         if ops.is_differentiable():
             # training: grouped features from the fused grouping kernel (constants w.r.t. the weights, as in the
@@ -620,9 +620,10 @@ class PositionalEncoding(nn.Module):
                 f2 = self.mlp2.forward_pooled(ops.query_lrf_group(pts, self.r2, self.ns2))
             return torch.cat([f1, f2], dim=1).transpose(1, 2)
         if pts.is_cuda and (torch.is_autocast_enabled() or ops.USE_F32X3) and self.r2 >= self.r1 and self.ns1 % 32 == 0 and self.ns2 % 32 == 0:
-            # the wide scale first: its neighbour lists are the candidates of the narrow scale (csrc/pe.hip)
-            f2, cand = ops.pe_group_mlp_max(pts, self.r2, self.ns2, self.mlp2, want_cand=True)
-            f1 = ops.pe_group_mlp_max(pts, self.r1, self.ns1, self.mlp1, cand_in=cand)
+            # one geometry launch for both scales (the wide scale's lists are the narrow one's candidates), then the two MLP launches (csrc/pe.hip)
+            g2, g1, _ = ops.pe_geometry(pts, self.r2, self.ns2, self.r1, self.ns1)
+            f2 = ops.pe_mlp_max(pts, self.r2, self.ns2, self.mlp2, g2)
+            f1 = ops.pe_mlp_max(pts, self.r1, self.ns1, self.mlp1, g1)
         else:
             f1 = ops.pe_group_mlp_max(pts, self.r1, self.ns1, self.mlp1)  # (B,N,128)
             f2 = ops.pe_group_mlp_max(pts, self.r2, self.ns2, self.mlp2)
@@ -635,10 +636,11 @@ class PositionalEncoding(nn.Module):
 
     def groups_split(self, pts, buf, b0):
         """`groups` of the clouds `pts` written into rows b0.. of `buf` ((Btot,N,512) bf16 = split layout of the (Btot,N,256) fp32
-        features): no concatenation of the scales, no fp32 round trip; two launches, no library kernel (side-stream safe)."""
+        features): no concatenation of the scales, no fp32 round trip; one geometry + two MLP launches, no library kernel (side-stream safe)."""
         pts = pts.float()
-        _, cand = ops.pe_group_mlp_max(pts, self.r2, self.ns2, self.mlp2, want_cand=True, out_split=(buf, b0, 128))
-        ops.pe_group_mlp_max(pts, self.r1, self.ns1, self.mlp1, cand_in=cand, out_split=(buf, b0, 0))
+        g2, g1, _ = ops.pe_geometry(pts, self.r2, self.ns2, self.r1, self.ns1)
+        ops.pe_mlp_max(pts, self.r2, self.ns2, self.mlp2, g2, out_split=(buf, b0, 128))
+        ops.pe_mlp_max(pts, self.r1, self.ns1, self.mlp1, g1, out_split=(buf, b0, 0))
         return buf
 
     def _mlp3_split(self):

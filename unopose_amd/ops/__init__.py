@@ -32,7 +32,7 @@ from .attention import (  # noqa: F401
 from .geometry import (  # noqa: F401
     lrf_global, query_lrf_group, lrf_group_idx, weighted_procrustes, cloud_radius, scale_by_radius, gather_rows, pairwise_distance,
     _bf16_split, _mfma_fragment_order, _GEO_HINV, _GEO_D_RANGE, _GEO_TABLE_UNAVAILABLE, _geo_tables, geo_embedding, geo_embedding_torch,
-    pe_group_mlp_max, pe_group_mlp_max_unfused, furthest_point_sample, _geo_grid, _GeoEmbedFn, geo_embedding_train_ok,
+    pe_group_mlp_max, pe_group_mlp_max_unfused, pe_geometry, pe_mlp_max, _pe_image, furthest_point_sample, _geo_grid, _GeoEmbedFn, geo_embedding_train_ok,
 )
 from .sampling import (  # noqa: F401
     bilinear_sample_native, sparse_upproj_ok, upproj_plan, sparse_pixel_features, bilinear_sample_pixels,

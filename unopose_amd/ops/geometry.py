@@ -286,24 +286,36 @@ def geo_embedding_torch(points, m):
     return d_emb + a_emb
 
 
-def pe_group_mlp_max(pts, radius, nsample, mlp, bf16x3=None, cand_in=None, want_cand=False, out_split=None):
-    """QueryAndLRFGroup -> SharedMLP[6,32,64,128] -> max over neighbours (fine matcher PE, Fi:167-174)
-    as ONE HIP kernel (csrc/pe.hip): neighbour lists, frames and all MLP activations stay on chip;
-    (B,N,3) -> (B,N,128) fp32.  Matrix-core precision: exact fp32 MFMA by default; under autocast(bf16)
-    (or bf16x3=True) bf16 MFMA with hi/lo-split operands (~2^-16 relative error, ~5x the fp32 MFMA rate).
-    Neighbour-list hand-off (bf16x3 kernel only): `want_cand=True` also returns (lists (B,N,nsample) int32,
-    counts (B,N) int32) of this pass; passing such a pair from a LARGER-radius pass over the same points as
-    `cand_in` lets this pass test those candidates instead of scanning the cloud (same result).
-    `out_split` = (buf (Btot,N,2W) bf16 viewed as the split layout of a W-wide fp32 row, first cloud b0, first channel c0):
-    the 128 channels go straight into that operand of csrc/gemm_f32.hip (bf16x3 kernel only); returns buf."""
-    if bf16x3 is None:  # the hi/lo-split matrix-core form is the fp32-class arithmetic of every other contraction of the fp32 path too
-        bf16x3 = torch.is_autocast_enabled() or st.USE_F32X3
-    if [tuple(l.conv.weight.shape[:2]) for l in mlp.layers()] != [(32, 6), (64, 32), (128, 64)] or nsample % 32:
-        note_fallback("pe_group_mlp_max", f"MLP widths / nsample {nsample} (kernel: 6-32-64-128, nsample % 32 == 0)")
-        return pe_group_mlp_max_unfused(pts, radius, nsample, mlp)  # other widths: grouping kernel + GEMMs
+def pe_geometry(pts, radius, nsample, radius2=0.0, nsample2=0, cand_in=None, want_cand=False):
+    """Neighbour lists, counts and local reference frames of every point of `pts` (B,N,3) for the bf16x3 PE path, in ONE launch
+    (csrc/pe.hip pe_geometry_kernel): per scale a tuple (lists (B,N,nsample) int16 holding 16-bit point ids, counts (B,N) int32
+    with -1 = more points inside the radius than the list holds, frames (B,N,9) fp32).  With nsample2 > 0 (radius2 <= radius) the
+    second scale of the same cloud is built in the same visit from the first one's lists.  `cand_in` = (lists int32, counts) of a
+    larger-radius pass; `want_cand` adds the first scale's lists as int32.  Returns (scale, scale2 or None, cand or None)."""
     pts = _c(pts.float())
     check_f32(pts, "pts")
     B, N, _ = pts.shape
+    dev = pts.device
+
+    def bufs(S):
+        return (torch.empty(B, N, int(S), dtype=torch.int16, device=dev), torch.empty(B, N, dtype=torch.int32, device=dev),
+                torch.empty(B, N, 9, dtype=torch.float32, device=dev))
+
+    with on_device(dev):
+        g1 = bufs(nsample)
+        g2 = bufs(nsample2) if nsample2 else None
+        cand = torch.empty(B, N, int(nsample), dtype=torch.int32, device=dev) if want_cand else None
+        ci = cand_in if cand_in is not None else (None, None)
+        assert ci[0] is None or (ci[0].is_contiguous() and ci[0].dtype == torch.int32 and ci[0].shape[:2] == (B, N) and ci[1].shape == (B, N))
+        n2 = (None, None, None) if g2 is None else tuple(ptr(t) for t in g2)
+        call("unopose_pe_geometry", ptr(pts), B, N, float(radius), int(nsample), float(radius2), int(nsample2),
+             None if ci[0] is None else ptr(ci[0]), None if ci[0] is None else ptr(ci[1]), 0 if ci[0] is None else int(ci[0].shape[2]),
+             ptr(g1[0]), ptr(g1[1]), ptr(g1[2]), None if cand is None else ptr(cand), *n2, stream_ptr())
+    return g1, g2, (None if cand is None else (cand, g1[1]))
+
+
+def _pe_image(mlp, dev):
+    """(key, folded fp32 weights, packed LDS weight image) of a SharedMLP[6,32,64,128], rebuilt when its parameters change."""
     cache = getattr(mlp, "_hip_cache", None)
     key = _params_key(mlp)  # (conv weights, BatchNorm affine AND running statistics)
     if cache is None or cache[0] != key:
@@ -314,44 +326,66 @@ def pe_group_mlp_max(pts, radius, nsample, mlp, bf16x3=None, cand_in=None, want_
                 flat += [w.float().contiguous(), b.float().contiguous()]
         assert [tuple(t.shape) for t in flat[::2]] == [(32, 6), (64, 32), (128, 64)], "kernel is built for [6,32,64,128]"
         from .._lib import lib
-        image = torch.empty(lib().unopose_pe_image_bytes(), dtype=torch.uint8, device=pts.device)
-        with on_device(pts.device):
+        image = torch.empty(lib().unopose_pe_image_bytes(), dtype=torch.uint8, device=dev)
+        with on_device(dev):
             call("unopose_pe_pack_weights", *(ptr(t) for t in flat), ptr(image), stream_ptr())
         cache = (key, flat, image)
         mlp._hip_cache = cache
-    w1, b1, w2, b2, w3, b3 = cache[1]
-    cand_out = None
-    if out_split is not None:
-        buf, b0, c0 = out_split
-        assert bf16x3 and buf.dtype == torch.bfloat16 and buf.is_contiguous() and buf.shape[1] == N and c0 % 32 == 0 and b0 + B <= buf.shape[0]
-        ld = buf.shape[2] // 2  # row width in 4-byte units
-        with on_device(pts.device):
-            if want_cand:
-                cand_out = (torch.empty(B, N, int(nsample), dtype=torch.int32, device=pts.device),
-                            torch.empty(B, N, dtype=torch.int32, device=pts.device))
-            ci = cand_in if cand_in is not None else (None, None)
+    return cache
+
+
+def pe_mlp_max(pts, radius, nsample, mlp, geom, out_split=None):
+    """SharedMLP[6,32,64,128] + max over the neighbour lists and frames `geom` = (lists, counts, frames) of `pe_geometry`
+    (csrc/pe.hip pe_group_mlp_max_bf16x3_kernel): (B,N,3) -> (B,N,128) fp32, or into `out_split` (see pe_group_mlp_max)."""
+    pts = _c(pts.float())
+    B, N, _ = pts.shape
+    lists, counts, frames = geom
+    assert lists.shape == (B, N, int(nsample)) and counts.shape == (B, N) and frames.shape == (B, N, 9)
+    cache = _pe_image(mlp, pts.device)
+    with on_device(pts.device):
+        if out_split is not None:
+            buf, b0, c0 = out_split
+            assert buf.dtype == torch.bfloat16 and buf.is_contiguous() and buf.shape[1] == N and c0 % 32 == 0 and b0 + B <= buf.shape[0]
+            ld = buf.shape[2] // 2  # row width in 4-byte units
             dst = ctypes.c_void_p(buf.data_ptr() + (b0 * N * ld + c0) * 4)
-            call("unopose_pe_group_mlp_max_packed_out", ptr(pts), B, N, float(radius), int(nsample), ptr(cache[2]),
-                 None if ci[0] is None else ptr(ci[0]), None if ci[0] is None else ptr(ci[1]),
-                 0 if ci[0] is None else int(ci[0].shape[2]), None if cand_out is None else ptr(cand_out[0]),
-                 None if cand_out is None else ptr(cand_out[1]), dst, ld, 1, stream_ptr())
-        return (buf, cand_out) if want_cand else buf
+            call("unopose_pe_mlp_max_packed", ptr(pts), B, N, float(radius), int(nsample), ptr(cache[2]), ptr(lists), ptr(counts),
+                 ptr(frames), dst, ld, 1, stream_ptr())
+            return buf
+        out = torch.empty(B, N, 128, dtype=torch.float32, device=pts.device)
+        call("unopose_pe_mlp_max_packed", ptr(pts), B, N, float(radius), int(nsample), ptr(cache[2]), ptr(lists), ptr(counts),
+             ptr(frames), ptr(out), 128, 0, stream_ptr())
+    return out
+
+
+def pe_group_mlp_max(pts, radius, nsample, mlp, bf16x3=None, cand_in=None, want_cand=False, out_split=None):
+    """QueryAndLRFGroup -> SharedMLP[6,32,64,128] -> max over neighbours (fine matcher PE, Fi:167-174)
+    in HIP kernels that keep all MLP activations on chip (csrc/pe.hip); (B,N,3) -> (B,N,128) fp32.  Matrix-core precision: exact
+    fp32 MFMA by default (ONE kernel: lists and frames stay on chip too); under autocast(bf16) (or bf16x3=True) bf16 MFMA with
+    hi/lo-split operands (~2^-16 relative error, ~5x the fp32 MFMA rate) as two launches, `pe_geometry` then `pe_mlp_max`.
+    Neighbour-list hand-off (bf16x3 only): `want_cand=True` also returns (lists (B,N,nsample) int32,
+    counts (B,N) int32) of this pass; passing such a pair from a LARGER-radius pass over the same points as
+    `cand_in` lets this pass test those candidates instead of scanning the cloud (same result).
+    `out_split` = (buf (Btot,N,2W) bf16 viewed as the split layout of a W-wide fp32 row, first cloud b0, first channel c0):
+    the 128 channels go straight into that operand of csrc/gemm_f32.hip (bf16x3 only); returns buf."""
+    if bf16x3 is None:  # the hi/lo-split matrix-core form is the fp32-class arithmetic of every other contraction of the fp32 path too
+        bf16x3 = torch.is_autocast_enabled() or st.USE_F32X3
+    if [tuple(l.conv.weight.shape[:2]) for l in mlp.layers()] != [(32, 6), (64, 32), (128, 64)] or nsample % 32:
+        note_fallback("pe_group_mlp_max", f"MLP widths / nsample {nsample} (kernel: 6-32-64-128, nsample % 32 == 0)")
+        return pe_group_mlp_max_unfused(pts, radius, nsample, mlp)  # other widths: grouping kernel + GEMMs
+    pts = _c(pts.float())
+    check_f32(pts, "pts")
+    B, N, _ = pts.shape
+    if bf16x3:
+        geom, _, cand_out = pe_geometry(pts, radius, nsample, cand_in=cand_in, want_cand=want_cand)
+        out = pe_mlp_max(pts, radius, nsample, mlp, geom, out_split=out_split)
+        return (out, cand_out) if want_cand else out
+    assert out_split is None, "out_split: bf16x3 kernel only"
+    w1, b1, w2, b2, w3, b3 = _pe_image(mlp, pts.device)[1]
     out = torch.empty(B, N, 128, dtype=torch.float32, device=pts.device)
     with on_device(pts.device):
-        if bf16x3:
-            if want_cand:
-                cand_out = (torch.empty(B, N, int(nsample), dtype=torch.int32, device=pts.device),
-                            torch.empty(B, N, dtype=torch.int32, device=pts.device))
-            ci = cand_in if cand_in is not None else (None, None)
-            assert ci[0] is None or (ci[0].is_contiguous() and ci[0].shape[:2] == (B, N) and ci[1].shape == (B, N))
-            call("unopose_pe_group_mlp_max_packed_cand", ptr(pts), B, N, float(radius), int(nsample), ptr(cache[2]),
-                 None if ci[0] is None else ptr(ci[0]), None if ci[0] is None else ptr(ci[1]),
-                 0 if ci[0] is None else int(ci[0].shape[2]), None if cand_out is None else ptr(cand_out[0]),
-                 None if cand_out is None else ptr(cand_out[1]), ptr(out), stream_ptr())
-        else:
-            call("unopose_pe_group_mlp_max", ptr(pts), B, N, float(radius), int(nsample), ptr(w1), ptr(b1), ptr(w2),
-                 ptr(b2), ptr(w3), ptr(b3), 0, ptr(out), stream_ptr())
-    return (out, cand_out) if want_cand else out
+        call("unopose_pe_group_mlp_max", ptr(pts), B, N, float(radius), int(nsample), ptr(w1), ptr(b1), ptr(w2),
+             ptr(b2), ptr(w3), ptr(b3), 0, ptr(out), stream_ptr())
+    return (out, None) if want_cand else out
 
 
 def pe_group_mlp_max_unfused(pts, radius, nsample, mlp, chunk=4):
