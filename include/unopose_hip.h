@@ -622,6 +622,29 @@ int unopose_linear_f32x3(const void *As, const void *Ws, const float *bias, floa
 int unopose_linear_f32x3_bf16(const void *As, const void *Ws, const float *bias, const void *resid, void *Cb, long M, int N, int K,
                               unopose_stream_t stream);
 
+/* Query-side instance preparation of the BOP test provider (unopose_amd/provider.py: get_instance) for all D detections of one image; every
+ * result equals the host provider's.  desc: D descriptors of unopose_prep_desc_ints() int32 each, laid out as csrc/prep.hip documents (window,
+ * offsets into masks / the compacted arrays / the row tables, resize mode and tap tables); the caller has range-checked them against H, W and
+ * the buffer sizes -- the kernels trust them.  masks: the windows' 0 / 1 bytes, row-major, back to back.
+ * _crop_resize: img (H, W, C) uint8 (C = 1 grey, 3, or 4 with the last channel ignored) -> out (D, 3, S, S) float32 = window -> (x mask when
+ *     use_mask) -> OpenCV's fixed-point INTER_LINEAR resize to S x S (taps: per distinct window side and axis, 4*S int32 [index 0 | index 1 |
+ *     weight 0 | weight 1]) -> lut[channel * 256 + value] (ToTensor + Normalize, filled by the provider's own function); bgr reverses channels.
+ * _compact_lift: the set mask pixels of each window in row-major order (row_base: per window row, the number of set pixels in the rows above)
+ *     -> pix (their flat window index, int32) and cloud (float64 x, y, z: ((u - cx) d) / fx, ((v - cy) d) / fy, d from depth (H, W) float64),
+ *     plus row_sums (3 float64 per window row).  _distances: dist = each point's float64 distance to its detection's centroid.
+ * _gather: P picked detections (sel: their window h, w), n drawn samples each (index: positions in the compacted arrays) -> pts (P, n, 3) float32,
+ *     choose (P, n) int64 = floor(r S / w) S + floor(c S / h) with (r, c) = divmod(pix, h), in float64. */
+int unopose_prep_desc_ints(void);
+int unopose_prep_crop_resize(const void *img, int H, int W, int C, const int *desc, const int *taps, const void *masks, const float *lut,
+                             int D, int S, int bgr, int use_mask, float *out, unopose_stream_t stream);
+int unopose_prep_compact_lift(const double *depth, int H, int W, const int *desc, const void *masks, const int *row_base, double fx,
+                              double fy, double cx, double cy, int D, int max_h, int *pix, double *cloud, double *row_sums,
+                              unopose_stream_t stream);
+int unopose_prep_distances(const int *desc, const double *cloud, const double *row_sums, int D, int max_n, double *dist,
+                           unopose_stream_t stream);
+int unopose_prep_gather(const int *sel, const int *index, const int *pix, const double *cloud, int P, int n, int S, float *pts, void *choose,
+                        unopose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

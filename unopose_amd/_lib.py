@@ -19,6 +19,7 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
 _L = ctypes.c_long
+_D = ctypes.c_double
 
 # name -> argtypes (return type is always int).  Must list every symbol that
 # include/unopose_hip.h declares; tests/test_abi.py checks the two agree.
@@ -121,6 +122,11 @@ SIGNATURES = {
     "unopose_geo_embedding_train_forward": [_P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _F, _F, _I, _P, _P, _P, _P],
     "unopose_geo_embedding_train_backward": [_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P],
     "unopose_geo_embedding_table": [_P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _I, _I, _P, _P, _P],
+    "unopose_prep_desc_ints": [],
+    "unopose_prep_crop_resize": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "unopose_prep_compact_lift": [_P, _I, _I, _P, _P, _P, _D, _D, _D, _D, _I, _I, _P, _P, _P, _P],
+    "unopose_prep_distances": [_P, _P, _P, _I, _I, _P, _P],
+    "unopose_prep_gather": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
 }
 
 

@@ -18,6 +18,7 @@
   reference; (2) the reference goes on to call the BOP evaluation (``bop_eval_utils``) after saving -- this entry stops at the CSV
   unless ``--eval`` is given, which scores it with ``unopose_amd.bop_eval`` (VSD + MSSD + MSPD -> AR, HIP depth renderer).
 * extras beyond the reference's line: ``--pipeline`` (two forwards in flight), ``--ref-cache`` (reference views encoded once),
+  ``--device-prep`` (the provider builds each image's query crops, clouds and pixel indices on the rank's GPU: same items, same rows),
   ``--print-plan`` (resolve config and paths, touch no GPU: used by the CPU tests)."""
 import argparse
 import ast
@@ -133,6 +134,7 @@ def main(argv=None):
     ap.add_argument("--eval-only", action="store_true", help="accepted for compatibility with main_unopose.py")
     ap.add_argument("--pipeline", action="store_true")
     ap.add_argument("--ref-cache", action="store_true")
+    ap.add_argument("--device-prep", action="store_true", help="build the query side of every item on the GPU (provider device path)")
     ap.add_argument("--print-plan", action="store_true")
     ap.add_argument("opts", nargs="*", help="key=value overrides")
     args = ap.parse_args(argv)
@@ -141,7 +143,8 @@ def main(argv=None):
     c = Cfg(cfg)
     if args.print_plan:
         print(json.dumps(dict(save_path=save_path, dataset=c.dataloader.test.dataset.eval_dataset_name, checkpoint=c.misc.load_from,
-                              amp=bool(c.test.amp.enabled), instance_batch_size=c.test.instance_batch_size, num_gpus=args.num_gpus)))
+                              amp=bool(c.test.amp.enabled), instance_batch_size=c.test.instance_batch_size, num_gpus=args.num_gpus,
+                              device_prep=bool(args.device_prep))))
         return 0
     if not osp.exists(c.misc.load_from):  # save_unopose.sh:15-18
         print(f"{c.misc.load_from} does not exist.", file=sys.stderr)
@@ -176,7 +179,7 @@ def main(argv=None):
         broadcast_module_(model, src=0)
     dcfg = dict(cfg["dataloader"]["test"]["dataset"])
     name, det_path = dcfg.pop("eval_dataset_name"), dcfg.pop("detetion_path", None)
-    dataset = BOPTestsetOneRef(dcfg.get("cfg", dcfg), name, det_path)
+    dataset = BOPTestsetOneRef(dcfg.get("cfg", dcfg), name, det_path, device=dev if args.device_prep else None)
 
     class Images:  # batch dim 1, like DataLoader(batch_size=1) over the dataset
         dets = getattr(dataset, "dets", None)

@@ -4,6 +4,7 @@
     geometry   frames, Procrustes, radius normalisation, gathers, geometric embedding, positional encoding
     sampling   pixel sampling and the sparse up-projection
     pose       similarity, assignment, coarse / fine pose heads
+    prep       query-side instance preparation of the BOP test provider (crops, clouds, pixel indices)
     train      autograd Functions of the training step
 Each function cites the reference Python it replaces.  Inputs must be CUDA tensors; there is no CPU path (RuntimeError).
 `from unopose_amd import ops; ops.linear(...)` keeps working as before the split; the A/B switches (ops.USE_LN_FOLD = False, ...) live in
@@ -40,6 +41,9 @@ from .sampling import (  # noqa: F401
 from .pose import (  # noqa: F401
     overlap_scores, set_first_rows_, pose_score, rigid_rows, feature_similarity, soft_assignment, coarse_pose_torch, fine_pose_torch, _assign_labels,
     coarse_pose, fine_pose, fine_pose_fused_ok, normalize_rows_bf16, normalize_rows_f32, fine_pose_from_features,
+)
+from .prep import (  # noqa: F401
+    PrepPlan, _desc_ints, _tap_table, prep_norm_table, _require, _result, prep_crop_resize, prep_lift, prep_gather,
 )
 from .train import (  # noqa: F401
     _InfoNCEFn, infonce_two_way, _BNReLUTrain, bn_relu, _BNReLUMaxPoolTrain, bn_relu_maxpool, _SaliencyFn, saliency_pair,

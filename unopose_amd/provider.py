@@ -345,6 +345,32 @@ class ReferenceViews:
         return dict(window=win, cloud=cloud.reshape(-1, 3), pixels=np.flatnonzero(inside), crop=crop, pose=pose)
 
 
+class _PinnedReturn:
+    """Device vector -> host through pinned buffers, each slot with an event of its own: `finish` waits for that one copy, not for
+    the device, so work enqueued after `start` runs while the host reads the values.  A slot's array is valid until the slot comes
+    round again."""
+
+    def __init__(self, slots=2):
+        self._slots, self._next = [None] * slots, 0
+
+    def start(self, t):
+        i, self._next = self._next, (self._next + 1) % len(self._slots)
+        if self._slots[i] is None or self._slots[i][0].numel() < t.numel() or self._slots[i][0].dtype != t.dtype:
+            self._slots[i] = (torch.empty(max(t.numel(), 1 << 16), dtype=t.dtype).pin_memory(), torch.cuda.Event())
+        buf, event = self._slots[i]
+        event.synchronize()  # the copy that last used this slot
+        view = buf[:t.numel()]
+        view.copy_(t, non_blocking=True)
+        event.record()
+        return view, event
+
+    @staticmethod
+    def finish(pending):
+        view, event = pending
+        event.synchronize()
+        return view.numpy()
+
+
 # ------------------------------------------------------------------------------------------------
 class BOPTestsetOneRef:
     """One item = one test image: all detections above `seg_filter_score` (or the best one), each paired
@@ -355,10 +381,18 @@ class BOPTestsetOneRef:
     rgb_to_bgr, obj_idxs, oneref_percat (+ targets_name, ref_scene_ims).
 
     `dets` maps "<scene:06d>_<image:06d>" to the image's detection dicts in file order (the runner deep-copies it
-    for the detections json, like ``data_loader.dataset.dets``)."""
+    for the detections json, like ``data_loader.dataset.dets``).
 
-    def __init__(self, cfg, eval_dataset_name="lmo", detetion_path=None):
+    `device`: a CUDA device turns on the device path of the query side: the per-pixel work of all detections of an image runs
+    in HIP kernels (ops/prep.py) and the item's `pts`, `rgb` and `rgb_choose` are tensors on that device, equal to the host
+    path's; every other key, the ``np.random`` stream and the control flow are the host path's (:meth:`_instances_device`)."""
+
+    def __init__(self, cfg, eval_dataset_name="lmo", detetion_path=None, device=None):
         assert detetion_path is not None
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != "cuda":
+            raise RuntimeError("BOPTestsetOneRef: device preparation on CPU not supported (leave `device` unset for the host path)")
+        self._device_image, self._distances = None, _PinnedReturn()
         opt = (lambda k, d=None: cfg.get(k, d)) if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
         self.cfg, self.dataset = cfg, eval_dataset_name
         for name in ("data_dir", "ref_targets_name", "rgb_mask_flag", "img_size", "n_sample_observed_point",
@@ -385,6 +419,8 @@ class BOPTestsetOneRef:
 
     # ---- one image --------------------------------------------------------------------------------------------
     def __getitem__(self, index):
+        if self.device is not None:
+            return self._getitem_device(index)
         key = self.det_keys[index]
         dets = self.dets[key]
         picked = [(i, inst) for i, inst in ((i, self.get_instance(d)) for i, d in enumerate(dets) if d["score"] > self.seg_filter_score)
@@ -449,6 +485,101 @@ class BOPTestsetOneRef:
             "tem1_pose": torch.FloatTensor(ref_pose),
             "ref_key": ref_key,
         }
+
+    # ---- the same, with the per-pixel work on the device -------------------------------------------------------
+    def _getitem_device(self, index):
+        key = self.det_keys[index]
+        dets = self.dets[key]
+        picked = self._instances_device(dets, [i for i, d in enumerate(dets) if d["score"] > self.seg_filter_score])
+        if picked is None:  # the same second pass as __getitem__: new draws for the best-scored detection
+            best = max(range(len(dets)), key=lambda i: (dets[i]["score"], -i))
+            picked = self._instances_device(dets, [best])
+            if picked is None:
+                raise ValueError(f"no qulified instance in {key}")
+        ids, insts, on_device = picked
+        item = {k: (on_device[k] if k in on_device else torch.stack([inst[k] for inst in insts])) for k in insts[0] if k != "ref_key"}
+        item["ref_keys"] = [inst["ref_key"] for inst in insts]
+        item["scene_id"] = torch.IntTensor([int(key[:6])])
+        item["img_id"] = torch.IntTensor([int(key[7:13])])
+        item["inst_ids"] = torch.IntTensor(ids)
+        item["seg_time"] = torch.FloatTensor([dets[0]["time"]])
+        return item
+
+    def _instances_device(self, dets, order):
+        """:meth:`get_instance` for the detections `order` of one image, in that order -> (their numbers, their host-side fields,
+        {pts, rgb, rgb_choose} stacked on the device) for those that survive, or None when none does.
+
+        ``np.random`` is consumed exactly as by the host path, which fixes the structure: detection k's radius threshold comes from
+        ITS reference draw and its query draw's size from its filtered count, so the draws of k follow those of k - 1 and cannot
+        move to the device.  Everything per pixel does not depend on a draw and runs first, for all detections at once (crops;
+        compaction, back-projection and distances); the distances come back in ONE pinned copy with an event of its own (a fixed
+        number of host waits per image, whatever the number of detections); the host then walks the detections as get_instance does
+        from the reference lookup on; one index table goes up and one gather produces the samples."""
+        from .ops import prep
+
+        cands = []  # (detection number, detection, window, window mask)
+        for i in order:
+            det = dets[i]
+            K, depth_scale = self.files.camera(self.data_folder, det["scene_id"], det["image_id"])
+            depth = self.files.depth_m(self.data_folder, det["scene_id"], det["image_id"], depth_scale)
+            valid = np.logical_and(rle_decode(det["segmentation"]) > 0, depth > 0)
+            if not np.sum(valid) > self.minimum_n_point:
+                continue  # None before any draw
+            win = Window.around(valid)
+            cands.append((i, det, win, win.crop(valid)))
+        if not cands:
+            return None  # nothing was uploaded or launched
+        scene_id, img_id = cands[0][1]["scene_id"], cands[0][1]["image_id"]  # `dets` are one image's
+        with torch.cuda.device(self.device):
+            colour_dev, depth_dev = self._image_on_device(scene_id, img_id, depth)
+            plan = prep.PrepPlan(depth.shape, [c[2] for c in cands], [c[3] for c in cands], self.img_size, self.device)
+            pix, cloud, dist = prep.prep_lift(depth_dev, K, plan)
+            pending = self._distances.start(dist)
+            crops = prep.prep_crop_resize(colour_dev, plan, bgr=self.rgb_to_bgr, use_mask=self.rgb_mask_flag)  # runs under the host's walk
+            dist = self._distances.finish(pending)
+            ids, insts, slots, index = [], [], [], []
+            for slot, (i, det, win, inside) in enumerate(cands):
+                obj_id = det["category_id"]
+                ref = self._reference_instance(scene_id, img_id, obj_id)
+                if ref is None:
+                    continue
+                ref_crop, ref_choose, ref_pts, ref_pose, ref_key = ref
+                radius = np.max(np.linalg.norm(ref_pts - np.mean(ref_pts, axis=0).reshape(1, 3), axis=1))
+                first = int(plan.pt_off[slot])
+                near = dist[first:first + int(plan.n[slot])] < 1.2 * radius
+                if np.sum(near) < self.minimum_n_point:
+                    continue
+                kept, n = np.flatnonzero(near), self.n_sample_observed_point
+                take = np.random.choice(np.arange(len(kept)), size=n, replace=len(kept) <= n)
+                ids.append(i)
+                slots.append(slot)
+                index.append(kept[take] + first)
+                insts.append({
+                    "pts": None, "rgb": None, "rgb_choose": None,  # on the device, below
+                    "obj": torch.IntTensor([self.obj_idxs[obj_id]]).long(),
+                    "obj_id": torch.IntTensor([obj_id]),
+                    "score": torch.FloatTensor([det["score"]]),
+                    "tem1_rgb": torch.FloatTensor(ref_crop),
+                    "tem1_choose": torch.IntTensor(ref_choose).long(),
+                    "tem1_pts": torch.FloatTensor(ref_pts),
+                    "tem1_pose": torch.FloatTensor(ref_pose),
+                    "ref_key": ref_key,
+                })
+            if not insts:
+                return None
+            pts, choose = prep.prep_gather(plan, slots, np.stack(index), pix, cloud)
+            if len(slots) < len(cands):
+                crops = crops[torch.as_tensor(slots, device=self.device)]
+        return ids, insts, {"pts": pts, "rgb": crops, "rgb_choose": choose}
+
+    def _image_on_device(self, scene_id, img_id, depth):
+        """Colour (uint8) and depth (float64 metres: float32 would not give the host path's bits) of the image, uploaded once."""
+        key = (scene_id, img_id)
+        if self._device_image is None or self._device_image[0] != key:
+            colour = np.ascontiguousarray(self.files.colour(self.data_folder, scene_id, img_id))
+            self._device_image = (key, torch.from_numpy(colour).to(self.device),
+                                  torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float64)).to(self.device))
+        return self._device_image[1:]
 
     def _ref_split_folder(self, ref_scene_id):
         """Where a reference scene lives: ycbv references outside the 12 test scenes and all tudl references come
