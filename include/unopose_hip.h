@@ -645,6 +645,23 @@ int unopose_prep_distances(const int *desc, const double *cloud, const double *r
 int unopose_prep_gather(const int *sel, const int *index, const int *pix, const double *cloud, int P, int n, int S, float *pts, void *choose,
                         unopose_stream_t stream);
 
+/* Pose errors of the BOP'19 scorer for P (estimate, ground truth) pairs per launch (csrc/bopscore.hip; unopose_amd/bop_eval.py's vsd / mssd /
+ * mspd are the specification, i.e. bop_toolkit_lib/pose_error.py:17-101, :104-153 with visibility.py:30-70 and misc.py:142-162).
+ * _vsd_counts: test (n_test,H,W), gt (n_gt,H,W), est (n_est,H,W) float32 depth maps (mm; the last two straight from unopose_render_depth);
+ *     index (P,3) int32 = the pair's map in each of the three (range-checked by the caller -- the kernel trusts them); pairs (P,6) float64 =
+ *     fx, fy, cx, cy, delta (visibility tolerance), diameter; taus: T <= 16 misalignment tolerances (HOST pointer, float64).  counts
+ *     (P, unopose_vsd_count_ints()) int32 = n_union, n_inter of the two visibility masks, then per tau the intersection pixels with
+ *     |dist_gt - dist_est| / diameter >= tau (columns past T stay 0).  Equal to numpy's counts, every cast and evaluation order kept.
+ *     Maps are read with 16-byte loads when H * W is a multiple of 4 and the three base pointers lie on 16-byte boundaries, else 4 bytes at a time.
+ * _pose_errors: pts (n,3) float64 model points; syms (S,12) float64 = row-major R then t of each symmetry (identity included); est, gt
+ *     (P,12) float64 poses laid out the same way; K (P,9) float64 row-major intrinsics -> mssd (P), mspd (P) float64 = min over symmetries
+ *     of the max over points of the 3-D / projected displacement (model units / pixels). */
+int unopose_vsd_count_ints(void);
+int unopose_vsd_counts(const float *test, int n_test, const float *gt, int n_gt, const float *est, int n_est, const int *index,
+                       const double *pairs, const double *taus, int T, int P, int H, int W, int *counts, unopose_stream_t stream);
+int unopose_pose_errors(const double *pts, int n, const double *syms, int S, const double *est, const double *gt, const double *K, int P,
+                        double *mssd, double *mspd, unopose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,9 @@ SIGNATURES = {
     "unopose_prep_compact_lift": [_P, _I, _I, _P, _P, _P, _D, _D, _D, _D, _I, _I, _P, _P, _P, _P],
     "unopose_prep_distances": [_P, _P, _P, _I, _I, _P, _P],
     "unopose_prep_gather": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "unopose_vsd_count_ints": [],
+    "unopose_vsd_counts": [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "unopose_pose_errors": [_P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P],
 }
 
 

@@ -11,7 +11,14 @@ ground-truth pose: `average_recall(..., renderer=..., depth_images=...)` takes a
 call -- `unopose_amd.render.HipDepthRenderer` is the HIP rasteriser (csrc/raster.hip); without a renderer AR_VSD and the BOP AR
 are None, never faked.  Pinned against bop_toolkit_lib's own `pose_error.vsd / mssd / mspd`, `pose_matching.match_poses_scene` and
 `score.calc_localization_scores` (tests/golden/make_bop_eval_golden.py; for VSD both sides score the same rendered depth).
-Host code (numpy): scoring runs once per result file, off the hot path; only the rasteriser is a device kernel."""
+Two routes to the same numbers: the host route (numpy per estimate; only the rasteriser is a device kernel) and, with
+`average_recall(..., device=...)`, the device route: depth maps stay on the GPU and csrc/bopscore.hip turns them into the integer counts
+of `vsd` and the `mssd` / `mspd` distances for many pairs per launch; the matching and the recall averaging are the same host code.
+`load_dataset` reads a BOP dataset folder for scoring (own PLY reader, symmetries as the toolkit lists them, targets file) and
+`score_csv` ties it to a result file, as the reference's test run does after saving (`--eval` of unopose_amd.cli)."""
+import json
+import os.path as osp
+
 import numpy as np
 
 MSSD_THRESHOLDS = np.arange(0.05, 0.51, 0.05)  # fractions of the object diameter
@@ -19,6 +26,11 @@ MSPD_THRESHOLDS = np.arange(5, 51, 5)          # pixels at 640 px image width
 VSD_TAUS = np.arange(0.05, 0.51, 0.05)         # misalignment tolerances, fractions of the object diameter
 VSD_THRESHOLDS = np.arange(0.05, 0.51, 0.05)   # correctness thresholds on the VSD error
 VSD_DELTA = 15.0                               # visibility tolerance in mm (every BOP dataset but ITODD: bop_eval_utils.py:348-362)
+VSD_DELTAS = {"itodd": 5.0}                    # the exception of that table
+# budget of the device route's depth maps alive at a time, rendered and test ones: about 218 maps of 480 x 640.  The index and count tensors
+# of a launch and one stacked copy of a chunk's test images come on top of it.
+DEVICE_CHUNK_BYTES = 256 << 20
+MAX_SYM_DISC_STEP = 0.01                       # the toolkit's discretisation of continuous symmetries (eval_bop19_pose.py)
 
 
 def read_results(path):
@@ -112,54 +124,35 @@ def _recall_at(per_image, threshold):
     return tp / targets if targets else 0.0
 
 
-def average_recall(results, scene_gt, models, cameras, im_width, n_top=1, renderer=None, depth_images=None, vsd_delta=VSD_DELTA):
-    """results: `read_results` rows; scene_gt[scene_id][im_id] = list of {"obj_id", "R" (3,3), "t" (3,) mm, optional "valid"};
-    models[obj_id] = {"pts" (n,3) mm, "diameter", "symmetries": [{"R","t"}] incl. identity}; cameras[scene_id][im_id] = K.
-    Only the `n_top` best-scored estimates per (image, object) take part (BOP: the instance count of the target).
-    With `renderer` (render_object(obj_id, R, t, fx, fy, cx, cy) -> {"depth"}) and depth_images[scene_id][im_id] (mm, (H,W)) the VSD
-    errors are computed too and "AR" = mean(AR_VSD, AR_MSSD, AR_MSPD) is the BOP'19 average recall; else AR_VSD = AR = None.
-    -> {"AR_VSD", "AR_MSSD", "AR_MSPD", "AR", "AR_MSSD_MSPD", "recalls_vsd" [tau][threshold], "recalls_mssd", "recalls_mspd"}."""
+def _walk(results, scene_gt, cameras, n_top, targets):
+    """The images, objects and `n_top` selection both routes score: yields (scene_id, im_id, ground truths with "valid" filled in, K,
+    [(obj_id, its estimates, best score first)]).  `targets[(scene_id, im_id)] = {obj_id: inst_count}` (the BOP targets file) limits the
+    scoring to these images and objects -- a ground truth of another object is not a target (valid = False) -- and bounds the selection:
+    n_top > 0 takes min(n_top, inst_count), n_top = -1 takes inst_count (the toolkit's "given by the number of GT poses"), 0 takes all.
+    Without `targets` every image of `scene_gt` is scored and any n_top <= 0 takes all."""
     by_im = {}
     for r in results:
         by_im.setdefault((r["scene_id"], r["im_id"]), []).append(r)
-    do_vsd = renderer is not None and depth_images is not None
-    sets = {"mssd": [], "mspd": []}
-    vsd_sets = [[] for _ in VSD_TAUS]
-    gt_depth = {}
     for sid, ims in scene_gt.items():
         for iid, gts in ims.items():
-            gts = [dict(g, valid=g.get("valid", True)) for g in gts]
+            wanted = None if targets is None else targets.get((sid, iid))
+            if targets is not None and wanted is None:
+                continue
+            gts = [dict(g, valid=g.get("valid", True) and (wanted is None or g["obj_id"] in wanted)) for g in gts]
             per_obj = {}
             for r in by_im.get((sid, iid), []):
-                per_obj.setdefault(r["obj_id"], []).append(r)
-            ests = {"mssd": [], "mspd": []}
-            vests = [[] for _ in VSD_TAUS]
-            K = np.asarray(cameras[sid][iid], np.float64)
+                if wanted is None or r["obj_id"] in wanted:
+                    per_obj.setdefault(r["obj_id"], []).append(r)
+            picked = []
             for obj_id, rows in per_obj.items():
-                rows = sorted(rows, key=lambda r: r["score"], reverse=True)[:n_top if n_top > 0 else None]
-                m = models[obj_id]
-                for r in rows:
-                    e1, e2, e3 = {}, {}, {}
-                    d_est = renderer.render_object(obj_id, r["R"], r["t"], K[0, 0], K[1, 1], K[0, 2], K[1, 2])["depth"] if do_vsd else None
-                    for gid, g in enumerate(gts):
-                        if g["obj_id"] != obj_id:
-                            continue
-                        Rg, tg = np.asarray(g["R"], np.float64), np.asarray(g["t"], np.float64)
-                        e1[gid] = mssd(r["R"], r["t"], Rg, tg, m["pts"], m["symmetries"]) / m["diameter"]
-                        e2[gid] = mspd(r["R"], r["t"], Rg, tg, K, m["pts"], m["symmetries"]) * (640.0 / im_width)
-                        if do_vsd:
-                            key = (sid, iid, gid)
-                            if key not in gt_depth:
-                                gt_depth[key] = renderer.render_object(obj_id, Rg, tg, K[0, 0], K[1, 1], K[0, 2], K[1, 2])["depth"]
-                            e3[gid] = vsd(d_est, gt_depth[key], depth_images[sid][iid], K, vsd_delta, VSD_TAUS, m["diameter"])
-                    ests["mssd"].append(dict(score=r["score"], errors=e1))
-                    ests["mspd"].append(dict(score=r["score"], errors=e2))
-                    for ti in range(len(VSD_TAUS)):
-                        vests[ti].append(dict(score=r["score"], errors={gid: e[ti] for gid, e in e3.items()}))
-            for k in sets:
-                sets[k].append((gts, ests[k]))
-            for ti in range(len(VSD_TAUS)):
-                vsd_sets[ti].append((gts, vests[ti]))
+                top = n_top if n_top > 0 else None
+                if wanted is not None:
+                    top = min(n_top, wanted[obj_id]) if n_top > 0 else wanted[obj_id] if n_top == -1 else None
+                picked.append((obj_id, sorted(rows, key=lambda r: r["score"], reverse=True)[:top]))
+            yield sid, iid, gts, np.asarray(cameras[sid][iid], np.float64), picked
+
+
+def _recall_tables(sets, vsd_sets, do_vsd):
     rec_s = [_recall_at(sets["mssd"], th) for th in MSSD_THRESHOLDS]
     rec_p = [_recall_at(sets["mspd"], th) for th in MSPD_THRESHOLDS]
     ar_s, ar_p = float(np.mean(rec_s)), float(np.mean(rec_p))
@@ -169,4 +162,400 @@ def average_recall(results, scene_gt, models, cameras, im_width, n_top=1, render
         rec_v = [[_recall_at(vsd_sets[ti], th) for th in VSD_THRESHOLDS] for ti in range(len(VSD_TAUS))]
         ar_v = float(np.mean(rec_v))
         out.update(recalls_vsd=rec_v, AR_VSD=ar_v, AR=float(np.mean([ar_v, ar_s, ar_p])))
+    return out
+
+
+def scored_pairs(walk):
+    """The (estimate, ground truth) pairs of a `_walk`, grouped as the device route renders them: one unit per (image, object) with
+    estimates AND ground truths -> [(scene_id, im_id, K, obj_id, estimates, [(gid, ground truth)])].  A pair's key is
+    (scene_id, im_id, obj_id, rank of the estimate among the object's picked ones, gid)."""
+    units = []
+    for sid, iid, gts, K, picked in walk:
+        for obj_id, rows in picked:
+            mine = [(gid, g) for gid, g in enumerate(gts) if g["obj_id"] == obj_id]
+            if rows and mine:
+                units.append((sid, iid, K, obj_id, rows, mine))
+    return units
+
+
+def _cuda_device(device):
+    import torch
+
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"bop_eval: the device route needs a CUDA device, not {device!r} (leave `device` unset for the host route)")
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+def device_pose_errors(units, models, device):
+    """`mssd` and `mspd` of every pair of `units` in model units / pixels: one `ops.pose_errors` launch per object.  -> {key: (mssd, mspd)}."""
+    from .ops.score import pose_errors
+
+    dev = _cuda_device(device)
+    by_obj = {}
+    for sid, iid, K, obj_id, rows, mine in units:
+        for rank, r in enumerate(rows):
+            for gid, g in mine:
+                by_obj.setdefault(obj_id, []).append(((sid, iid, obj_id, rank, gid), r, g, K))
+    out, pending = {}, []
+    for obj_id, pairs in by_obj.items():
+        m = models[obj_id]
+        pending.append((pairs, pose_errors(m["pts"], m["symmetries"], [p[1]["R"] for p in pairs], [p[1]["t"] for p in pairs], [p[2]["R"] for p in pairs],
+                                           [p[2]["t"] for p in pairs], [p[3] for p in pairs], dev)))
+    for pairs, (e_s, e_p) in pending:  # read back after everything is queued
+        for p, a, b in zip(pairs, e_s.cpu().numpy(), e_p.cpu().numpy()):
+            out[p[0]] = (float(a), float(b))
+    return out
+
+
+def device_vsd_counts(units, models, renderer, depth_images, vsd_delta, device, chunk_bytes=DEVICE_CHUNK_BYTES):
+    """The integer counts of `vsd` for every pair of `units`, from maps that never leave the device.  Every estimate is rendered once and
+    every (image, ground truth) once, each image's test depth is uploaded once, and pairs are processed in chunks whose rendered and
+    test maps fit `chunk_bytes`: a chunk is a run of whole (image, object) units, rendered with one `render_batch` per object and side
+    and counted with one `ops.vsd_counts` launch per object.  Only a unit that exceeds the budget on its own is split, its ground
+    truths rendered again per piece.  -> ({key: int64 array (2 + len(VSD_TAUS),) = n_union, n_inter, count per tau}, number of chunks)."""
+    import torch
+
+    from .ops.score import vsd_counts
+    from .render import HipDepthRenderer
+
+    dev = _cuda_device(device)
+    if not isinstance(renderer, HipDepthRenderer) or _cuda_device(renderer.device) != dev:
+        raise RuntimeError(f"bop_eval: VSD on the device route needs a render.HipDepthRenderer on {dev}, not {type(renderer).__name__}"
+                           f"{' on ' + str(renderer.device) if isinstance(renderer, HipDepthRenderer) else ''}; there is no fallback to the host route")
+    H, W = renderer.H, renderer.W
+    budget = min(max(3, int(chunk_bytes) // (4 * H * W)), 65535)  # maps alive at a time: one test image, one ground truth and one estimate at least
+    pieces = []
+    for unit in units:
+        rows, mine = unit[4], unit[5]
+        step = len(rows) if 1 + len(mine) + len(rows) <= budget else max(1, budget - 1 - len(mine))
+        pieces += [(unit, first, min(first + step, len(rows))) for first in range(0, len(rows), step)]
+    chunks, used, images = [], budget + 1, set()
+    for piece in pieces:
+        (sid, iid, _, _, _, mine), first, last = piece
+        need = len(mine) + last - first
+        if used + need + ((sid, iid) not in images) > budget:
+            chunks.append([])
+            used, images = 0, set()
+        used += need + ((sid, iid) not in images)
+        images.add((sid, iid))
+        chunks[-1].append(piece)
+    out, on_dev = {}, {}
+    for chunk in chunks:
+        order = list(dict.fromkeys((p[0][0], p[0][1]) for p in chunk))
+        on_dev = {k: v for k, v in on_dev.items() if k in order}  # an image shared with the previous chunk is not uploaded again
+        for sid, iid in order:
+            if (sid, iid) not in on_dev:
+                d = np.ascontiguousarray(np.asarray(depth_images[sid][iid], dtype=np.float32))
+                if d.shape != (H, W):
+                    raise RuntimeError(f"bop_eval: depth image {sid}/{iid} is {d.shape}, the renderer {(H, W)}")
+                on_dev[(sid, iid)] = torch.from_numpy(d).to(dev)
+        test = on_dev[order[0]][None] if len(order) == 1 else torch.stack([on_dev[k] for k in order])
+        by_obj = {}
+        for piece in chunk:
+            by_obj.setdefault(piece[0][3], []).append(piece)
+        pending = []
+        for obj_id, group in by_obj.items():
+            est, gt, gt_at, keys, index, K4, diam = [], [], {}, [], [], [], models[obj_id]["diameter"]
+            for (sid, iid, K, _, rows, mine), first, last in group:
+                k4 = [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]
+                for gid, g in mine:
+                    if (sid, iid, gid) not in gt_at:
+                        gt_at[(sid, iid, gid)] = len(gt)
+                        gt.append((g["R"], g["t"], k4))
+                for rank in range(first, last):
+                    est.append((rows[rank]["R"], rows[rank]["t"], k4))
+                    for gid, _ in mine:
+                        keys.append((sid, iid, obj_id, rank, gid))
+                        index.append((order.index((sid, iid)), gt_at[(sid, iid, gid)], len(est) - 1))
+                        K4.append(k4)
+            d_gt = renderer.render_batch(obj_id, np.stack([p[0] for p in gt]), np.stack([p[1] for p in gt]), np.asarray([p[2] for p in gt]))
+            d_est = renderer.render_batch(obj_id, np.stack([p[0] for p in est]), np.stack([p[1] for p in est]), np.asarray([p[2] for p in est]))
+            index, K4 = np.asarray(index), np.asarray(K4)
+            for a in range(0, len(keys), 65535):  # the launch limit of pairs
+                b = slice(a, a + 65535)
+                pending.append((keys[b], vsd_counts(test, d_gt, d_est, K4[b], vsd_delta, diam, VSD_TAUS, index[b, 0], index[b, 1], index[b, 2])))
+        for keys, counts in pending:  # one read-back per chunk, after its launches are queued; the maps are released with the chunk
+            out.update(zip(keys, counts.cpu().numpy()))
+    return out, len(chunks)
+
+
+def _host_errors(walk, models, im_width, renderer, depth_images, vsd_delta):
+    """The host route: errors of every scored pair with numpy, one estimate at a time -> {key: (mssd / diameter, mspd at 640 px width, VSD
+    error per tau or None)}, keys as `scored_pairs` documents them.  Every estimate is rendered once, every (image, ground truth) once."""
+    out, gt_depth = {}, {}
+    for sid, iid, gts, K, picked in walk:
+        for obj_id, rows in picked:
+            m = models[obj_id]
+            for rank, r in enumerate(rows):
+                d_est = renderer.render_object(obj_id, r["R"], r["t"], K[0, 0], K[1, 1], K[0, 2], K[1, 2])["depth"] if renderer is not None else None
+                for gid, g in enumerate(gts):
+                    if g["obj_id"] != obj_id:
+                        continue
+                    Rg, tg = np.asarray(g["R"], np.float64), np.asarray(g["t"], np.float64)
+                    e1 = mssd(r["R"], r["t"], Rg, tg, m["pts"], m["symmetries"]) / m["diameter"]
+                    e2 = mspd(r["R"], r["t"], Rg, tg, K, m["pts"], m["symmetries"]) * (640.0 / im_width)
+                    e3 = None
+                    if renderer is not None:
+                        key = (sid, iid, gid)
+                        if key not in gt_depth:
+                            gt_depth[key] = renderer.render_object(obj_id, Rg, tg, K[0, 0], K[1, 1], K[0, 2], K[1, 2])["depth"]
+                        e3 = vsd(d_est, gt_depth[key], depth_images[sid][iid], K, vsd_delta, VSD_TAUS, m["diameter"])
+                    out[(sid, iid, obj_id, rank, gid)] = (e1, e2, e3)
+    return out
+
+
+def _device_errors(walk, models, im_width, renderer, depth_images, vsd_delta, device, chunk_bytes):
+    """Errors of every scored pair as the host loop forms them: {key: (mssd / diameter, mspd at 640 px width, VSD error per tau or None)}.
+    The VSD error comes from the integer counts exactly as in `vsd`: (count + n_union - n_inter) / n_union, 1.0 for an empty union."""
+    units = scored_pairs(walk)
+    if not units:
+        return {}
+    dist = device_pose_errors(units, models, device)
+    counts = device_vsd_counts(units, models, renderer, depth_images, vsd_delta, device, chunk_bytes)[0] if renderer is not None else None
+    out = {}
+    for key, (e_s, e_p) in dist.items():
+        e_v = None
+        if counts is not None:
+            n_union, n_inter, *per_tau = (int(c) for c in counts[key])
+            e_v = [1.0] * len(per_tau) if n_union == 0 else [float((c + (n_union - n_inter)) / float(n_union)) for c in per_tau]
+        out[key] = (e_s / models[key[2]]["diameter"], e_p * (640.0 / im_width), e_v)
+    return out
+
+
+def average_recall(results, scene_gt, models, cameras, im_width, n_top=1, renderer=None, depth_images=None, vsd_delta=VSD_DELTA, device=None,
+                   targets=None, chunk_bytes=DEVICE_CHUNK_BYTES):
+    """results: `read_results` rows; scene_gt[scene_id][im_id] = list of {"obj_id", "R" (3,3), "t" (3,) mm, optional "valid"};
+    models[obj_id] = {"pts" (n,3) mm, "diameter", "symmetries": [{"R","t"}] incl. identity}; cameras[scene_id][im_id] = K.
+    Only the `n_top` best-scored estimates per (image, object) take part (BOP: the instance count of the target; `targets`: see `_walk`).
+    With `renderer` (render_object(obj_id, R, t, fx, fy, cx, cy) -> {"depth"}) and depth_images[scene_id][im_id] (mm, (H,W)) the VSD
+    errors are computed too and "AR" = mean(AR_VSD, AR_MSSD, AR_MSPD) is the BOP'19 average recall; else AR_VSD = AR = None.
+    Without `device` the errors come from `_host_errors` (numpy); a CUDA `device` selects `_device_errors`: same walk, same matching, the errors from csrc/bopscore.hip; VSD
+    then needs a `render.HipDepthRenderer` of the image size on that device, and at most `chunk_bytes` of rendered maps exist at a time.
+    The device route reads the test depth as float32, which is what `load_dataset` and the toolkit's `load_depth` return.
+    -> {"AR_VSD", "AR_MSSD", "AR_MSPD", "AR", "AR_MSSD_MSPD", "recalls_vsd" [tau][threshold], "recalls_mssd", "recalls_mspd"}."""
+    do_vsd = renderer is not None and depth_images is not None
+    walk = list(_walk(results, scene_gt, cameras, n_top, targets))
+    if device is None:
+        errors = _host_errors(walk, models, im_width, renderer if do_vsd else None, depth_images, vsd_delta)
+    else:
+        errors = _device_errors(walk, models, im_width, renderer if do_vsd else None, depth_images, vsd_delta, device, chunk_bytes)
+    sets = {"mssd": [], "mspd": []}
+    vsd_sets = [[] for _ in VSD_TAUS]
+    for sid, iid, gts, K, picked in walk:
+        ests = {"mssd": [], "mspd": []}
+        vests = [[] for _ in VSD_TAUS]
+        for obj_id, rows in picked:
+            for rank, r in enumerate(rows):
+                mine = {gid: errors[(sid, iid, obj_id, rank, gid)] for gid, g in enumerate(gts) if g["obj_id"] == obj_id}
+                ests["mssd"].append(dict(score=r["score"], errors={gid: e[0] for gid, e in mine.items()}))
+                ests["mspd"].append(dict(score=r["score"], errors={gid: e[1] for gid, e in mine.items()}))
+                for ti in range(len(VSD_TAUS)):
+                    vests[ti].append(dict(score=r["score"], errors={gid: e[2][ti] for gid, e in mine.items()} if do_vsd else {}))
+        for k in sets:
+            sets[k].append((gts, ests[k]))
+        for ti in range(len(VSD_TAUS)):
+            vsd_sets[ti].append((gts, vests[ti]))
+    return _recall_tables(sets, vsd_sets, do_vsd)
+
+
+# ---- reading a BOP dataset folder for scoring ----------------------------------------------------------------------------------
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply(path):
+    """A PLY mesh, ASCII or binary_little_endian, with scalar vertex properties (x, y, z among them) and triangular faces (one list
+    property, `vertex_indices` / `vertex_index`) -> {"pts" (V,3) float64, "faces" (F,3) int32}.  Elements other than vertex and face may
+    follow them and are not read; anything else in the file is an error, not a guess."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    body = data.find(b"\n", end) + 1
+    fmt, elements = None, []
+    for line in data[:end].decode("latin-1").splitlines():
+        w = line.split()
+        if not w or w[0] in ("ply", "comment", "obj_info"):
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == "property" and elements:
+            elements[-1][2].append(tuple(w[1:]))
+        else:
+            raise ValueError(f"{path}: header line {line!r}")
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: PLY format {fmt!r} (ascii and binary_little_endian are read)")
+    out = {"faces": np.zeros((0, 3), np.int32)}
+    tokens, at = (data[body:].split(), 0) if fmt == "ascii" else (None, body)
+    for name, count, props in elements:
+        if name not in ("vertex", "face"):
+            if "pts" not in out:
+                raise ValueError(f"{path}: element {name!r} before the vertices")
+            break
+        lists = [p for p in props if p[0] == "list"]
+        unknown = [t for p in props for t in (p[1:3] if p[0] == "list" else p[:1]) if t not in _PLY_TYPES]
+        if unknown or any(len(p) != (4 if p[0] == "list" else 2) for p in props):
+            raise ValueError(f"{path}: {name} properties {props}")
+        if name == "vertex":
+            if lists or not {"x", "y", "z"} <= {p[1] for p in props}:
+                raise ValueError(f"{path}: vertex properties {props}")
+            dtype = np.dtype([(p[1], "<" + _PLY_TYPES[p[0]]) for p in props])
+        else:
+            if len(props) != 1 or not lists or props[0][3] not in ("vertex_indices", "vertex_index"):
+                raise ValueError(f"{path}: face properties {props} (one list of vertex indices is read)")
+            dtype = np.dtype([("n", "<" + _PLY_TYPES[props[0][1]]), ("v", "<" + _PLY_TYPES[props[0][2]], (3,))])
+        if fmt == "ascii":
+            width = len(props) if name == "vertex" else 4
+            rows = np.array(tokens[at:at + count * width], dtype=np.float64).reshape(count, width)
+            if name == "face" and count and (rows[:, 0] != 3).any():
+                raise ValueError(f"{path}: a face that is not a triangle")  # rows of another length also misalign the reshape above
+            at += count * width
+            rec = {p[1]: rows[:, i] for i, p in enumerate(props)} if name == "vertex" else {"v": rows[:, 1:]}
+        else:
+            if at + count * dtype.itemsize > len(data):
+                raise ValueError(f"{path}: truncated {name} data")
+            rec = np.frombuffer(data, dtype=dtype, count=count, offset=at)
+            at += count * dtype.itemsize
+            if name == "face" and count and (rec["n"] != 3).any():
+                raise ValueError(f"{path}: a face that is not a triangle")
+        if name == "vertex":
+            out["pts"] = np.stack([np.asarray(rec[k], np.float64) for k in "xyz"], axis=1)
+        else:
+            out["faces"] = np.asarray(rec["v"]).astype(np.int32).reshape(count, 3)
+    if "pts" not in out:
+        raise ValueError(f"{path}: no vertex element")
+    if len(out["faces"]) and (out["faces"].min() < 0 or out["faces"].max() >= len(out["pts"])):
+        raise ValueError(f"{path}: face index outside the {len(out['pts'])} vertices")
+    return out
+
+
+def _axis_rotation(angle, axis):
+    d = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    skew = np.array([[0.0, -d[2], d[1]], [d[2], 0.0, -d[0]], [-d[1], d[0], 0.0]])
+    return np.cos(angle) * np.eye(3) + (1.0 - np.cos(angle)) * np.outer(d, d) + np.sin(angle) * skew
+
+
+def symmetry_transformations(model_info, max_sym_disc_step=MAX_SYM_DISC_STEP):
+    """The toolkit's `misc.get_symmetry_transformations` (misc.py:44-91): the identity and `symmetries_discrete`, each combined with
+    every step of every `symmetries_continuous` axis discretised into ceil(pi / max_sym_disc_step) rotations -> [{"R" (3,3), "t" (3,)}],
+    identity first."""
+    disc = [dict(R=np.eye(3), t=np.zeros(3))]
+    for sym in model_info.get("symmetries_discrete", []):
+        m = np.reshape(np.asarray(sym, np.float64), (4, 4))
+        disc.append(dict(R=m[:3, :3], t=m[:3, 3]))
+    cont = []
+    for sym in model_info.get("symmetries_continuous", []):
+        offset = np.asarray(sym["offset"], np.float64).reshape(3)
+        steps = int(np.ceil(np.pi / max_sym_disc_step))
+        for i in range(steps):
+            R = _axis_rotation(i * (2.0 * np.pi / steps), sym["axis"])
+            cont.append(dict(R=R, t=-R.dot(offset) + offset))
+    if not cont:
+        return disc
+    return [dict(R=c["R"].dot(d["R"]), t=c["R"].dot(d["t"]) + c["t"]) for d in disc for c in cont]
+
+
+class _SceneDepth:
+    def __init__(self, owner, scene_id):
+        self.owner, self.scene_id = owner, scene_id
+
+    def __getitem__(self, im_id):
+        return self.owner.image(self.scene_id, im_id)
+
+
+class DepthImages:
+    """depth_images[scene_id][im_id] -> the test depth in mm (float32, file value x depth_scale as the toolkit's `load_depth` then
+    `*= depth_scale`), read when asked for and kept behind `provider.SceneFiles`' LRU rule."""
+
+    def __init__(self, folder, depth_scales, max_images=16):
+        from collections import OrderedDict
+
+        self.folder, self.depth_scales, self.max_images, self._store = folder, depth_scales, max_images, OrderedDict()
+
+    def __getitem__(self, scene_id):
+        return _SceneDepth(self, scene_id)
+
+    def image(self, scene_id, im_id):
+        from .provider import SceneFiles, read_image
+
+        def make():
+            base = osp.join(self.folder, f"{scene_id:06d}", "depth", f"{im_id:06d}")
+            d = read_image(base + ".png" if osp.exists(base + ".png") else base + ".tif").astype(np.float32)
+            d *= self.depth_scales[scene_id][im_id]
+            return d
+
+        return SceneFiles._lru(self._store, (scene_id, im_id), self.max_images, make)
+
+
+def dataset_paths(root, name, split, targets_filename="test_targets_bop19.json"):
+    """The files and folders `load_dataset` reads."""
+    base = osp.join(root, name)
+    return dict(targets=osp.join(base, targets_filename), models_info=osp.join(base, "models_eval", "models_info.json"),
+                models=osp.join(base, "models_eval"), split=osp.join(base, split))
+
+
+def load_dataset(root, name, split, targets_filename="test_targets_bop19.json"):
+    """What `average_recall` needs of the BOP dataset `<root>/<name>`, for the images and objects of the targets file:
+    models[obj_id] = {"pts", "verts", "faces", "diameter", "symmetries"} from models_eval/obj_XXXXXX.ply + models_info.json;
+    scene_gt / cameras / depth_scales[scene_id][im_id] from <split>/<scene>/scene_gt.json and scene_camera.json; depth_images: a lazy
+    `DepthImages`; targets[(scene_id, im_id)] = {obj_id: inst_count}; im_size = (W, H) of the first target's depth image."""
+    from .provider import SceneFiles, load_json
+
+    paths = dataset_paths(root, name, split, targets_filename)
+    targets = {}
+    for t in load_json(paths["targets"]):
+        targets.setdefault((int(t["scene_id"]), int(t["im_id"])), {})[int(t["obj_id"])] = int(t.get("inst_count", 1))
+    info = load_json(paths["models_info"])
+    models = {}
+    for obj_id in sorted({o for objs in targets.values() for o in objs}):
+        mesh = read_ply(osp.join(paths["models"], f"obj_{obj_id:06d}.ply"))
+        models[obj_id] = dict(pts=mesh["pts"], verts=mesh["pts"], faces=mesh["faces"], diameter=float(info[str(obj_id)]["diameter"]),
+                              symmetries=symmetry_transformations(info[str(obj_id)]))
+    files = SceneFiles()
+    scene_gt, cameras, depth_scales = {}, {}, {}
+    for sid, iid in targets:
+        gts = files.scene_json(paths["split"], sid, "scene_gt.json")[str(iid)]
+        scene_gt.setdefault(sid, {})[iid] = [dict(obj_id=int(g["obj_id"]), R=np.asarray(g["cam_R_m2c"], np.float64).reshape(3, 3),
+                                                  t=np.asarray(g["cam_t_m2c"], np.float64).reshape(3)) for g in gts]
+        K, scale = files.camera(paths["split"], sid, iid)
+        cameras.setdefault(sid, {})[iid] = np.asarray(K, np.float64)
+        depth_scales.setdefault(sid, {})[iid] = float(scale)
+    depth_images = DepthImages(paths["split"], depth_scales)
+    im_size = None
+    if targets:
+        sid, iid = next(iter(targets))
+        im_size = depth_images[sid][iid].shape[::-1]
+    return dict(models=models, scene_gt=scene_gt, cameras=cameras, depth_scales=depth_scales, depth_images=depth_images, targets=targets,
+                im_size=im_size)
+
+
+def score_csv(csv_path, root, name, split, device="cuda", device_scoring=True, n_top=-1, vsd_delta=None,
+              targets_filename="test_targets_bop19.json", renderer=None, chunk_bytes=DEVICE_CHUNK_BYTES):
+    """Score the result file `csv_path` against the BOP dataset `<root>/<name>` and write `scores_bop19.json` beside it: the AR values
+    and recall tables of `average_recall`, the number of scored targets ((image, object) entries of the targets file) and estimates,
+    and the settings.  `device`: the GPU that renders (`render.HipDepthRenderer`, unless a `renderer` is handed in) and, with
+    `device_scoring`, computes the errors; device_scoring=False is the host scorer on the same renders.  n_top as in `_walk` (-1: the
+    targets' instance counts); vsd_delta defaults to the dataset's (15 mm, ITODD 5 mm).  -> the dictionary written."""
+    data = load_dataset(root, name, split, targets_filename)
+    results = read_results(csv_path)
+    vsd_delta = VSD_DELTAS.get(name, VSD_DELTA) if vsd_delta is None else vsd_delta
+    W, H = data["im_size"]
+    if renderer is None:
+        from .render import HipDepthRenderer
+
+        renderer = HipDepthRenderer(W, H, device=_cuda_device(device))
+    for obj_id, m in data["models"].items():
+        renderer.add_object(obj_id, m["verts"], m["faces"])
+    out = average_recall(results, data["scene_gt"], data["models"], data["cameras"], W, n_top=n_top, renderer=renderer,
+                         depth_images=data["depth_images"], vsd_delta=vsd_delta, device=device if device_scoring else None,
+                         targets=data["targets"], chunk_bytes=chunk_bytes)
+    scored = sum(len(rows) for *_, picked in _walk(results, data["scene_gt"], data["cameras"], n_top, data["targets"]) for _, rows in picked)
+    out.update(n_targets=sum(len(objs) for objs in data["targets"].values()), n_estimates=len(results), n_scored_estimates=scored, dataset=name,
+               split=split, n_top=n_top, vsd_delta=float(vsd_delta), scorer="device" if device_scoring else "host")
+    with open(osp.join(osp.dirname(osp.abspath(csv_path)), "scores_bop19.json"), "w") as f:
+        json.dump(out, f, indent=1)
     return out

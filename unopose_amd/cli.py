@@ -15,8 +15,13 @@
   InferenceSampler rule and rows gathered to rank 0.
 * two deliberate differences from ``engine.do_save_results``: (1) ``test.amp.enabled=True`` selects **bf16** autocast here (the reference's
   ``torch.cuda.amp.autocast`` is fp16; bf16 is what the MI355X kernels are built and parity-tested for), ``False`` = fp32 as in the
-  reference; (2) the reference goes on to call the BOP evaluation (``bop_eval_utils``) after saving -- this entry stops at the CSV
-  unless ``--eval`` is given, which scores it with ``unopose_amd.bop_eval`` (VSD + MSSD + MSPD -> AR, HIP depth renderer).
+  reference; (2) the reference always goes on to the BOP evaluation (``bop_eval_utils``) after saving -- this entry stops at the CSV
+  unless ``--eval`` is given.  Then rank 0 scores the CSV with ``unopose_amd.bop_eval.score_csv`` on its GPU (VSD + MSSD + MSPD -> AR;
+  HIP depth renderer, pose errors in HIP kernels; ``--eval-device-off`` keeps the renders but computes the errors on the host, for
+  comparison), writes ``scores_bop19.json`` beside the CSV and prints one line with AR_VSD / AR_MSSD / AR_MSPD / AR.  It reads
+  ``<data_dir>/<dataset>``: ``bop_eval.targets_filename`` (default ``test_targets_bop19.json``), ``models_eval/``, the ``bop_eval.split``
+  folder; ``bop_eval.n_top`` (default -1: the targets' instance counts) and ``bop_eval.vsd_delta`` (default 15 mm, ITODD 5 mm,
+  bop_eval_utils.py:348-362) are spelled as in the reference's ``val_cfg``.
 * extras beyond the reference's line: ``--pipeline`` (two forwards in flight), ``--ref-cache`` (reference views encoded once),
   ``--device-prep`` (the provider builds each image's query crops, clouds and pixel indices on the rank's GPU: same items, same rows),
   ``--print-plan`` (resolve config and paths, touch no GPU: used by the CPU tests)."""
@@ -80,6 +85,21 @@ def result_paths(cfg, iteration=None):
     return out_dir, osp.join(out_dir, name)
 
 
+def eval_settings(cfg):
+    """What ``--eval`` hands to ``bop_eval.score_csv``: the dataset folder of the provider and the ``bop_eval`` keys of the reference's
+    ``val_cfg`` (bop_eval_utils.py:340-366)."""
+    from .bop_eval import VSD_DELTA, VSD_DELTAS
+
+    dcfg = cfg["dataloader"]["test"]["dataset"]
+    name = dcfg["eval_dataset_name"]
+    data_dir = dcfg.get("cfg", dcfg).get("data_dir")
+    if data_dir is None:
+        raise ValueError("--eval: dataloader.test.dataset has no data_dir")
+    be = cfg.get("bop_eval", {})
+    return dict(root=data_dir, name=name, split=be.get("split", "test"), targets_filename=be.get("targets_filename", "test_targets_bop19.json"),
+                n_top=int(be.get("n_top", -1)), vsd_delta=float(be.get("vsd_delta", VSD_DELTAS.get(name, VSD_DELTA))))
+
+
 def _launch_ranks(n, argv, poll_s=0.2):
     """N fresh interpreters with the torchrun environment contract; the parent has not initialised HIP.  All children are polled:
     when any one exits non-zero the others are terminated and that code is returned (as torchrun does) -- a rank that dies must not
@@ -128,13 +148,15 @@ def load_checkpoint(model, path):
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m unopose_amd.cli", description=__doc__.split("\n\n")[0],
                                  epilog="Differences from engine.do_save_results: test.amp.enabled=True means bf16 autocast (reference: fp16); "
-                                        "the BOP evaluation is not started after saving (see unopose_amd.bop_eval).")
+                                        "the BOP evaluation is started after saving only with --eval (unopose_amd.bop_eval.score_csv).")
     ap.add_argument("--config-file", required=True)
     ap.add_argument("--num-gpus", type=int, default=1)
     ap.add_argument("--eval-only", action="store_true", help="accepted for compatibility with main_unopose.py")
     ap.add_argument("--pipeline", action="store_true")
     ap.add_argument("--ref-cache", action="store_true")
     ap.add_argument("--device-prep", action="store_true", help="build the query side of every item on the GPU (provider device path)")
+    ap.add_argument("--eval", action="store_true", help="score the CSV after saving (BOP'19 AR; rank 0, on its GPU)")
+    ap.add_argument("--eval-device-off", action="store_true", help="with --eval: compute the pose errors on the host (same renders), for comparison")
     ap.add_argument("--print-plan", action="store_true")
     ap.add_argument("opts", nargs="*", help="key=value overrides")
     args = ap.parse_args(argv)
@@ -142,9 +164,16 @@ def main(argv=None):
     out_dir, save_path = result_paths(cfg)
     c = Cfg(cfg)
     if args.print_plan:
-        print(json.dumps(dict(save_path=save_path, dataset=c.dataloader.test.dataset.eval_dataset_name, checkpoint=c.misc.load_from,
-                              amp=bool(c.test.amp.enabled), instance_batch_size=c.test.instance_batch_size, num_gpus=args.num_gpus,
-                              device_prep=bool(args.device_prep))))
+        plan = dict(save_path=save_path, dataset=c.dataloader.test.dataset.eval_dataset_name, checkpoint=c.misc.load_from,
+                    amp=bool(c.test.amp.enabled), instance_batch_size=c.test.instance_batch_size, num_gpus=args.num_gpus,
+                    device_prep=bool(args.device_prep), eval=bool(args.eval))
+        if args.eval:
+            from .bop_eval import dataset_paths
+
+            ev = eval_settings(cfg)
+            plan.update(eval_device=not args.eval_device_off, eval_paths=dataset_paths(ev["root"], ev["name"], ev["split"], ev["targets_filename"]),
+                        eval_scores=osp.join(out_dir, "scores_bop19.json"), eval_n_top=ev["n_top"], eval_vsd_delta=ev["vsd_delta"])
+        print(json.dumps(plan))
         return 0
     if not osp.exists(c.misc.load_from):  # save_unopose.sh:15-18
         print(f"{c.misc.load_from} does not exist.", file=sys.stderr)
@@ -204,6 +233,14 @@ def main(argv=None):
         pipe.close()
     if lines is not None:
         print(f"{len(lines)} estimates -> {save_path}")
+    if args.eval and int(os.environ.get("RANK", "0")) == 0:  # the other ranks wait at the teardown below
+        from .bop_eval import score_csv
+
+        ev = eval_settings(cfg)
+        sc = score_csv(save_path, ev["root"], ev["name"], ev["split"], device=dev, device_scoring=not args.eval_device_off, n_top=ev["n_top"],
+                       vsd_delta=ev["vsd_delta"], targets_filename=ev["targets_filename"])
+        print("BOP19 %s-%s: AR_VSD %.4f  AR_MSSD %.4f  AR_MSPD %.4f  AR %.4f  (%d targets, %d estimates scored on the %s)"
+              % (ev["name"], ev["split"], sc["AR_VSD"], sc["AR_MSSD"], sc["AR_MSPD"], sc["AR"], sc["n_targets"], sc["n_scored_estimates"], sc["scorer"]))
     if world > 1:
         dist.destroy_process_group()
     return 0

@@ -1,0 +1,104 @@
+"""Pose errors of the BOP'19 scorer on the device (csrc/bopscore.hip): the integer counts inside `bop_eval.vsd` and the
+`bop_eval.mssd` / `mspd` errors, for many (estimate, ground truth) pairs per launch.  `bop_eval`'s host functions are the
+specification: the counts equal numpy's, the two distances agree with the BLAS-backed host code to rounding.
+
+The kernels trust the map indices they are given: the wrappers check every index against the map stacks on the host BEFORE
+anything is launched.  Depth maps are CUDA tensors; the small per-pair tables are host arrays; there is no CPU path."""
+import ctypes
+import functools
+
+import numpy as np
+import torch
+
+from .._lib import call, lib, on_device, ptr, stream_ptr
+
+MAX_TAUS = 16
+
+
+@functools.lru_cache(maxsize=None)
+def _count_ints():
+    return int(lib().unopose_vsd_count_ints())
+
+
+def _maps(x, name, hw=None):
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError(f"{name}: CPU not supported")
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 3 or x.shape[0] < 1:
+        raise RuntimeError(f"{name} must be a contiguous float32 tensor (maps, H, W), not {x.dtype} {tuple(x.shape)}")
+    if hw is not None and tuple(x.shape[1:]) != tuple(hw):
+        raise RuntimeError(f"{name}: maps of {tuple(x.shape[1:])}, expected {tuple(hw)}")
+    return x
+
+
+def _index(idx, P, limit, name):
+    idx = np.arange(P, dtype=np.int64) if idx is None else np.asarray(idx, dtype=np.int64).reshape(-1)
+    if idx.shape[0] != P or idx.min() < 0 or idx.max() >= limit:
+        raise ValueError(f"vsd_counts: {name} must hold {P} indices inside [0, {limit})")
+    return idx
+
+
+def vsd_delta_as_compared(delta):
+    """`_visib_mask` compares a float32 difference with `delta`: numpy does that in float32 for a Python number and in float64 for
+    a float64 array scalar.  The kernel compares in float64, with `delta` rounded the way numpy would have."""
+    return float(np.result_type(np.float32, delta).type(delta))
+
+
+def vsd_counts(depth_test, depth_gt, depth_est, K4, delta, diameter, taus, image_index=None, gt_index=None, est_index=None):
+    """The counts of `bop_eval.vsd` for P pairs over one image size.  depth_test (n_test, H, W), depth_gt (n_gt, H, W), depth_est
+    (n_est, H, W): float32 CUDA maps in mm, the rendered ones straight from `HipDepthRenderer.render_batch`; pair p scores
+    depth_est[est_index[p]] against depth_gt[gt_index[p]] in front of depth_test[image_index[p]] (each index defaults to p).  K4 (P, 4) or
+    (4,) = fx, fy, cx, cy; delta, diameter: scalars or (P,); taus: T <= 16 tolerances.
+    -> int64 CUDA tensor (P, 2 + T): n_union, n_inter, then per tau the intersection pixels with |dist_gt - dist_est| / diameter >= tau."""
+    _maps(depth_test, "vsd_counts: depth_test")
+    hw = tuple(depth_test.shape[1:])
+    _maps(depth_gt, "vsd_counts: depth_gt", hw), _maps(depth_est, "vsd_counts: depth_est", hw)
+    dev = depth_test.device
+    if depth_gt.device != dev or depth_est.device != dev:
+        raise RuntimeError("vsd_counts: the maps live on different devices")
+    taus = np.ascontiguousarray(np.asarray(taus, dtype=np.float64).reshape(-1))
+    T = taus.shape[0]
+    if not 1 <= T <= MAX_TAUS:
+        raise ValueError(f"vsd_counts: {T} taus (1 .. {MAX_TAUS})")
+    P = len(est_index) if est_index is not None else len(gt_index) if gt_index is not None else int(depth_est.shape[0])
+    if not 1 <= P <= 65535:
+        raise ValueError(f"vsd_counts: {P} pairs per call (1 .. 65535)")
+    index = np.stack([_index(image_index, P, depth_test.shape[0], "image_index"), _index(gt_index, P, depth_gt.shape[0], "gt_index"),
+                      _index(est_index, P, depth_est.shape[0], "est_index")], axis=1).astype(np.int32)
+    pairs = np.empty((P, 6), dtype=np.float64)
+    pairs[:, :4] = np.asarray(K4, dtype=np.float64).reshape(-1, 4)
+    pairs[:, 4] = [vsd_delta_as_compared(d) for d in delta] if np.ndim(delta) else vsd_delta_as_compared(delta)
+    pairs[:, 5] = np.asarray(diameter, dtype=np.float64)
+    index_d, pairs_d = torch.from_numpy(index).to(dev), torch.from_numpy(pairs).to(dev)
+    n = _count_ints()
+    counts = torch.empty(P, n, dtype=torch.int32, device=dev)
+    with on_device(dev):
+        call("unopose_vsd_counts", ptr(depth_test), int(depth_test.shape[0]), ptr(depth_gt), int(depth_gt.shape[0]), ptr(depth_est),
+             int(depth_est.shape[0]), ptr(index_d), ptr(pairs_d), ctypes.c_void_p(taus.ctypes.data), T, P, hw[0], hw[1], ptr(counts), stream_ptr(dev))
+    return counts[:, :2 + T].to(torch.int64)
+
+
+def pose_errors(pts, symmetries, R_est, t_est, R_gt, t_gt, K, device):
+    """`bop_eval.mssd` and `bop_eval.mspd` for P pairs of one object.  pts (n, 3) model points; symmetries: list of {"R", "t"} with the
+    identity; R_est, R_gt (P, 3, 3), t_est, t_gt (P, 3); K (P, 3, 3) or (3, 3) -- host arrays, float64 on the device.
+    -> (mssd (P,), mspd (P,)) float64 CUDA tensors, in model units and pixels."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("pose_errors: CPU not supported")
+    pts = np.ascontiguousarray(np.asarray(pts, dtype=np.float64).reshape(-1, 3))
+    syms = np.stack([np.concatenate([np.asarray(s["R"], np.float64).reshape(9), np.asarray(s["t"], np.float64).reshape(3)]) for s in symmetries])
+    R_est, R_gt = np.asarray(R_est, np.float64).reshape(-1, 9), np.asarray(R_gt, np.float64).reshape(-1, 9)
+    P = R_est.shape[0]
+    if P < 1 or R_gt.shape[0] != P or pts.shape[0] < 1:
+        raise ValueError(f"pose_errors: {P} estimates, {R_gt.shape[0]} ground truths, {pts.shape[0]} points")
+    poses = np.concatenate([R_est, np.asarray(t_est, np.float64).reshape(P, 3), R_gt, np.asarray(t_gt, np.float64).reshape(P, 3)], axis=1)
+    K = np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 9), (P, 9))
+    host = np.concatenate([pts.reshape(-1), syms.reshape(-1), poses[:, :12].reshape(-1), poses[:, 12:].reshape(-1), K.reshape(-1)])
+    buf = torch.from_numpy(host).to(dev)  # one upload
+    o = np.cumsum([0, pts.size, syms.size, 12 * P, 12 * P, 9 * P])
+    part = [buf[o[i]:o[i + 1]] for i in range(5)]
+    out = torch.empty(2, P, dtype=torch.float64, device=dev)
+    with on_device(dev):
+        call("unopose_pose_errors", ptr(part[0]), pts.shape[0], ptr(part[1]), syms.shape[0], ptr(part[2]), ptr(part[3]), ptr(part[4]), P,
+             ptr(out[0]), ptr(out[1]), stream_ptr(dev))
+    return out[0], out[1]
+
