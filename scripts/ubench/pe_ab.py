@@ -7,6 +7,9 @@
 (whatever launches that call makes in that tree), the two-scale `PositionalEncoding.groups_split` path and, where the tree has it,
 the geometry kernel alone, then writes features, lists and counts on: the bench clouds (B = 32, both scales, fp32 and split output),
 `norm_clouds(2048, 3, seed=5)` with duplicated points, and the edge clouds of tests/test_model_gpu.py's grid-query test.
+It also writes `ops.query_lrf_group` at (r 0.1, S 64) and (r 0.2, S 256) on all of those clouds, at (r 0.2, S 40) on
+`norm_clouds(777, 3, seed=11)`, and one `ops.lrf_group_idx` result on the inputs of tests/test_geom_gpu.py's "other options" test.
+The library is TREE's own, or the one UNOPOSE_LIB names (another build of the same ABI under TREE's Python).
 """
 import os
 import sys
@@ -113,6 +116,17 @@ for kind, y in clouds.items():
             wide = (l, c)
         else:
             out[f"{kind}.S{S}.feat_from_wide"] = ops.pe_group_mlp_max(y, r, S, mlp, bf16x3=True, cand_in=wide)
+# the unfused grouping kernel (training path, `_ext`-level API): its own ball query, and lists handed in
+clouds["bench"] = x
+for kind, y in clouds.items():
+    for r, S in ((0.1, 64), (0.2, 256)):
+        out[f"{kind}.query_lrf_group.S{S}"] = ops.query_lrf_group(y.cuda().contiguous(), r, S)
+out["n777.query_lrf_group.S40"] = ops.query_lrf_group(norm_clouds(777, 3, seed=11).cuda(), 0.2, 40)
+from unopose_amd.pointnet2 import _ext  # noqa: E402
+
+xo = norm_clouds(1024, 2, seed=5, repl_every=9).cuda()
+new = (xo + 0.03 * torch.randn(xo.shape, generator=torch.Generator().manual_seed(6)).cuda()).contiguous()
+out["shifted.lrf_group_idx.S32"] = ops.lrf_group_idx(xo, new, _ext.ball_query(new, xo, 0.2, 32), 0.2)
 torch.cuda.synchronize()
 os.makedirs(outdir, exist_ok=True)
 torch.save({k: v.cpu() for k, v in out.items()}, os.path.join(outdir, "pe_ab.pt"))

@@ -139,12 +139,16 @@ def test_query_lrf_group_golden(name, expect):
     _check_group(out, z["out"], z["radius"], expect)
 
 
-@pytest.mark.parametrize("r,ns,expect", [(0.1, 64, (0.9321, 0.9712, 0.4658)), (0.2, 256, (0.9858, 0.9951, 0.9697))])
-def test_query_lrf_group_full_size_vs_oracle(oracle_ext, r, ns, expect):
+# N = 777: not a multiple of 64, a list shorter than a wave, and centres that fill the list early (12 %: 40 or more points inside the
+# radius) beside padded ones (the smallest neighbourhood holds 3 points): the tail guards of the ball query's multi-step scan
+@pytest.mark.parametrize("N,r,ns,expect", [(2048, 0.1, 64, (0.9321, 0.9712, 0.4658)), (2048, 0.2, 256, (0.9858, 0.9951, 0.9697)),
+                                           (777, 0.2, 40, (0.9820, 0.9846, 0.8378))],
+                         ids=["0.1-64-expect0", "0.2-256-expect1", "N777-0.2-40"])  # (the 2048-point cases keep the ids they had)
+def test_query_lrf_group_full_size_vs_oracle(oracle_ext, N, r, ns, expect):
     from unopose_amd import ops
     from oracle import unopose_ref as R
 
-    x = norm_clouds(2048, 3, seed=11)
+    x = norm_clouds(N, 3, seed=11)
     out = ops.query_lrf_group(x.cuda(), r, ns).cpu()
     ref = R.query_and_lrf_group(x, r, ns, oracle_ext)
     _check_group(out, ref, r, expect)

@@ -4,12 +4,15 @@
 //   * unopose_query_lrf_group   -- QueryAndLRFGroup.forward = ball_query + group + LRF_batch
 //                                  (pointnet2/pointnet2_utils.py:429-481, 522-584) in ONE kernel:
 //                                  the neighbour list never leaves LDS.
+//                                  Neighbour list and frame are lrf.h's, the code pe.hip runs too; only the x axis'
+//                                  normalisation differs (finish_frame below).
 //   * unopose_weighted_procrustes -- weighted_procrustes (utils/model_utils.py:667-743)
 // All 3x3 eigen / singular problems are solved by Jacobi rotations in registers
 // (jacobi3.h) instead of torch.svd.
 
 #include "common.h"
 #include "jacobi3.h"
+#include "lrf.h"
 
 namespace unopose {
 
@@ -30,6 +33,8 @@ __device__ __forceinline__ float block_max_256(float v, float *red) {
 
 // Frame construction shared by the global and the per-point LRF, given
 //   z  : sign-resolved normal,  acc : sum_i alpha_i beta_i v_i  (model_utils.py:804-812)
+// x = acc / (|acc| + 1e-10) by MULTIPLICATION with the reciprocal here, by division in pe.hip's pe_frame_axes: the two forms differ in
+// the last bit.  Each is kept because the outputs of its kernels are pinned (golden fixtures, bit-identity records under profiles/).
 __device__ __forceinline__ void finish_frame(Vec3 z, Vec3 acc, Vec3 &xp, Vec3 &yp) {
   const float n = sqrtf(dot(acc, acc)) + 1e-10f;
   xp = scale(acc, 1.f / n);
@@ -122,15 +127,9 @@ __global__ __launch_bounds__(256) void query_lrf_group_kernel(const float *__res
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int *nbr = nbr_all + wave * S;
   const float *P = xyz + (size_t)b * N * 3;
-  for (int e = tid; e < N * 3; e += 256) {
-    const float v = P[e];
-    const int p = e / 3, comp = e - p * 3;
-    (comp == 0 ? sx : comp == 1 ? sy : sz)[p] = v;
-  }
+  for (int e = tid; e < N * 3; e += 256) lrf_stage_coord(sx, sy, sz, e, P[e]);
   __syncthreads();
   const float r2 = radius * radius;
-  const float inv_r = 1.f / radius;  // NB reference divides; see below (division kept for parity)
-  (void)inv_r;
   const size_t chan = (size_t)N * S;
   float *O = out + (size_t)b * 6 * chan;
 
@@ -139,7 +138,6 @@ __global__ __launch_bounds__(256) void query_lrf_group_kernel(const float *__res
     if (j >= N) break;  // wave-uniform
     const float cx = sx[j], cy = sy[j], cz = sz[j];
     float qx = cx, qy = cy, qz = cz;  // the centre channels 0-2 are relative to
-    int cnt = 0, first = 0;
     if constexpr (IDX) {
       const float *q = new_xyz + ((size_t)b * N + j) * 3;
       qx = q[0]; qy = q[1]; qz = q[2];
@@ -148,78 +146,18 @@ __global__ __launch_bounds__(256) void query_lrf_group_kernel(const float *__res
         const int k = row_in[l];
         nbr[l] = (unsigned)k < (unsigned)N ? k : 0;
       }
-      cnt = S;
+      wave_lds_handover();
+    } else {
+      lrf_ball_query<int, int>(sx, sy, sz, N, S, r2, lane, cx, cy, cz, nbr, nullptr, -1, LrfGrid{}, false);
     }
-    // ---- ball query: first S hits in index order, tail padded with the first hit
-    for (int k0 = 0; !IDX && k0 < N && cnt < S; k0 += 64) {
-      const int k = k0 + lane;
-      bool hit = false;
-      if (k < N) {
-        const float x = sx[k], y = sy[k], z = sz[k];
-        const float d2 = (cx - x) * (cx - x) + (cy - y) * (cy - y) + (cz - z) * (cz - z);
-        hit = d2 < r2;
-      }
-      const unsigned long long mask = __ballot(hit);
-      if (mask) {
-        const int pre =
-            (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-        const int pos = cnt + pre;
-        if (hit && pos < S) nbr[pos] = k;
-        if (cnt == 0) first = k0 + __builtin_ctzll(mask);
-        cnt += __builtin_popcountll(mask);
-      }
-    }
-    for (int l = min(cnt, S) + lane; l < S; l += 64) nbr[l] = first;  // cnt == 0 -> index 0 (zero row)
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-    // ---- covariance of x = c - p_k over the S (padded) neighbours
-    float a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0;
-    for (int l = lane; l < S; l += 64) {
-      const int k = nbr[l];
-      const float x = cx - sx[k], y = cy - sy[k], z = cz - sz[k];
-      a00 += x * x; a01 += x * y; a02 += x * z; a11 += y * y; a12 += y * z; a22 += z * z;
-    }
-    const float inv_s = 1.f / (float)S;
-    a00 = wave_sum_f32(a00) * inv_s;
-    a01 = wave_sum_f32(a01) * inv_s;
-    a02 = wave_sum_f32(a02) * inv_s;
-    a11 = wave_sum_f32(a11) * inv_s;
-    a12 = wave_sum_f32(a12) * inv_s;
-    a22 = wave_sum_f32(a22) * inv_s;
+    float a00, a01, a02, a11, a12, a22;
+    lrf_covariance(sx, sy, sz, S, lane, cx, cy, cz, nbr, a00, a01, a02, a11, a12, a22);
     Vec3 e0, e1, z0;
     float l0, l1, l2;
     eig_sym3(a00, a01, a02, a11, a12, a22, e0, e1, z0, l0, l1, l2);
-
-    int vote = 0;
-    for (int l0i = 0; l0i < S; l0i += 64) {
-      const int l = l0i + lane;
-      float pr = 0.f;
-      if (l < S) {
-        const int k = nbr[l];
-        pr = z0.x * (cx - sx[k]) + z0.y * (cy - sy[k]) + z0.z * (cz - sz[k]);
-      }
-      vote += __builtin_popcountll(__ballot(pr > 1e-3f)) - __builtin_popcountll(__ballot(pr < -1e-3f));
-    }
-    const Vec3 zp = vote < 0 ? scale(z0, -1.f) : z0;
-
-    float vx = 0, vy = 0, vz = 0;
-    for (int l = lane; l < S; l += 64) {
-      const int k = nbr[l];
-      const Vec3 xn = v3(sx[k] - cx, sy[k] - cy, sz[k] - cz);
-      const float nrm = dot(zp, xn);
-      const Vec3 vi = sub(xn, scale(zp, nrm));
-      float alpha = radius - sqrtf(dot(xn, xn));
-      alpha *= alpha;
-      const float ab = alpha * (nrm * nrm);
-      vx += ab * vi.x; vy += ab * vi.y; vz += ab * vi.z;
-    }
-    vx = wave_sum_f32(vx);
-    vy = wave_sum_f32(vy);
-    vz = wave_sum_f32(vz);
-    Vec3 xp, yp;
-    finish_frame(zp, v3(vx, vy, vz), xp, yp);
+    Vec3 xp, yp, zp, acc;
+    lrf_vote_xacc(sx, sy, sz, S, radius, lane, cx, cy, cz, nbr, z0, zp, acc);
+    finish_frame(zp, acc, xp, yp);
 
     float *row = O + (size_t)j * S;
     for (int l = lane; l < S; l += 64) {
@@ -238,6 +176,21 @@ __global__ __launch_bounds__(256) void query_lrf_group_kernel(const float *__res
 }
 
 // -------------------------------------------------- weighted Procrustes -----
+// H += a b^T (a = centred source point, b = weighted centred reference point)
+__device__ __forceinline__ void procrustes_accumulate(float (&h)[9], float a0, float a1, float a2, float b0, float b1, float b2) {
+  h[0] += a0 * b0; h[1] += a0 * b1; h[2] += a0 * b2;
+  h[3] += a1 * b0; h[4] += a1 * b1; h[5] += a1 * b2;
+  h[6] += a2 * b0; h[7] += a2 * b1; h[8] += a2 * b2;
+}
+// t = c_ref - R c_src (s = c_src, r = c_ref).  (The nine stores of R stay in the kernels: inside this function they reorder the
+// instruction streams of the wave and thread kernels.)
+__device__ __forceinline__ void procrustes_translation(const float (&R)[9], float s0, float s1, float s2, float r0, float r1, float r2,
+                                                       float *to) {
+  to[0] = r0 - (R[0] * s0 + R[1] * s1 + R[2] * s2);
+  to[1] = r1 - (R[3] * s0 + R[4] * s1 + R[5] * s2);
+  to[2] = r2 - (R[6] * s0 + R[7] * s1 + R[8] * s2);
+}
+
 // R, t with ref ~ R src + t (model_utils.py:667-743).  One wavefront per problem.
 __global__ __launch_bounds__(256) void procrustes_wave_kernel(const float *__restrict__ src,
                                                               const float *__restrict__ ref,
@@ -272,9 +225,7 @@ __global__ __launch_bounds__(256) void procrustes_wave_kernel(const float *__res
     wi = (wi < thresh ? 0.f : wi) * inv;
     const float a0 = S[i * 3 + 0] - s0, a1 = S[i * 3 + 1] - s1, a2 = S[i * 3 + 2] - s2;
     const float b0 = wi * (Rf[i * 3 + 0] - r0), b1 = wi * (Rf[i * 3 + 1] - r1), b2 = wi * (Rf[i * 3 + 2] - r2);
-    h[0] += a0 * b0; h[1] += a0 * b1; h[2] += a0 * b2;
-    h[3] += a1 * b0; h[4] += a1 * b1; h[5] += a1 * b2;
-    h[6] += a2 * b0; h[7] += a2 * b1; h[8] += a2 * b2;
+    procrustes_accumulate(h, a0, a1, a2, b0, b1, b2);
   }
 #pragma unroll
   for (int i = 0; i < 9; ++i) h[i] = wave_sum_f32(h[i]);
@@ -284,10 +235,7 @@ __global__ __launch_bounds__(256) void procrustes_wave_kernel(const float *__res
     float *Ro = Rout + (size_t)m * 9;
 #pragma unroll
     for (int i = 0; i < 9; ++i) Ro[i] = R[i];
-    float *to = tout + (size_t)m * 3;
-    to[0] = r0 - (R[0] * s0 + R[1] * s1 + R[2] * s2);
-    to[1] = r1 - (R[3] * s0 + R[4] * s1 + R[5] * s2);
-    to[2] = r2 - (R[6] * s0 + R[7] * s1 + R[8] * s2);
+    procrustes_translation(R, s0, s1, s2, r0, r1, r2, tout + (size_t)m * 3);
   }
 }
 
@@ -359,9 +307,7 @@ __global__ __launch_bounds__(256) void procrustes_block_kernel(const float *__re
   for (int k = 0; k < PPT; ++k) {
     const float a0 = sp[k][0] - s0, a1 = sp[k][1] - s1, a2 = sp[k][2] - s2;
     const float b0 = wi[k] * (rp[k][0] - r0), b1 = wi[k] * (rp[k][1] - r1), b2 = wi[k] * (rp[k][2] - r2);
-    h[0] += a0 * b0; h[1] += a0 * b1; h[2] += a0 * b2;
-    h[3] += a1 * b0; h[4] += a1 * b1; h[5] += a1 * b2;
-    h[6] += a2 * b0; h[7] += a2 * b1; h[8] += a2 * b2;
+    procrustes_accumulate(h, a0, a1, a2, b0, b1, b2);
   }
   block_sum(h, 9);
   if (tid == 0) {
@@ -370,10 +316,7 @@ __global__ __launch_bounds__(256) void procrustes_block_kernel(const float *__re
     float *Ro = Rout + (size_t)m * 9;
 #pragma unroll
     for (int i = 0; i < 9; ++i) Ro[i] = R[i];
-    float *to = tout + (size_t)m * 3;
-    to[0] = r0 - (R[0] * s0 + R[1] * s1 + R[2] * s2);
-    to[1] = r1 - (R[3] * s0 + R[4] * s1 + R[5] * s2);
-    to[2] = r2 - (R[6] * s0 + R[7] * s1 + R[8] * s2);
+    procrustes_translation(R, s0, s1, s2, r0, r1, r2, tout + (size_t)m * 3);
   }
 }
 
@@ -409,24 +352,36 @@ __global__ __launch_bounds__(256) void procrustes_thread_kernel(const float *__r
     const float a0 = S[i * 3 + 0] - s0, a1 = S[i * 3 + 1] - s1, a2 = S[i * 3 + 2] - s2;
     const float b0 = wi[i] * (Rf[i * 3 + 0] - r0), b1 = wi[i] * (Rf[i * 3 + 1] - r1),
                 b2 = wi[i] * (Rf[i * 3 + 2] - r2);
-    h[0] += a0 * b0; h[1] += a0 * b1; h[2] += a0 * b2;
-    h[3] += a1 * b0; h[4] += a1 * b1; h[5] += a1 * b2;
-    h[6] += a2 * b0; h[7] += a2 * b1; h[8] += a2 * b2;
+    procrustes_accumulate(h, a0, a1, a2, b0, b1, b2);
   }
   float R[9];
   kabsch_from_H(h, R);
   float *Ro = Rout + (size_t)m * 9;
 #pragma unroll
   for (int i = 0; i < 9; ++i) Ro[i] = R[i];
-  float *to = tout + (size_t)m * 3;
-  to[0] = r0 - (R[0] * s0 + R[1] * s1 + R[2] * s2);
-  to[1] = r1 - (R[3] * s0 + R[4] * s1 + R[5] * s2);
-  to[2] = r2 - (R[6] * s0 + R[7] * s1 + R[8] * s2);
+  procrustes_translation(R, s0, s1, s2, r0, r1, r2, tout + (size_t)m * 3);
 }
 
 }  // namespace unopose
 
 using namespace unopose;
+
+// query_lrf_group (IDX = false: the kernel's own ball query around the points) and lrf_group_idx (IDX = true: the caller's lists)
+template <bool IDX>
+static int launch_query_lrf_group(const float *xyz, const float *new_xyz, const int *idx, int B, int N, float radius, int nsample,
+                                  float *out, unopose_stream_t stream) {
+  constexpr const char *what = IDX ? "lrf_group_idx" : "query_lrf_group";
+  UNOPOSE_REQUIRE(xyz && out && (!IDX || (new_xyz && idx)), "%s: null pointer", what);
+  UNOPOSE_REQUIRE(B >= 0 && N >= 1 && nsample >= 1 && B <= 65535, "%s: bad sizes", what);
+  if (B == 0) return UNOPOSE_OK;
+  const size_t lds = ((size_t)3 * N + 4 * (size_t)nsample) * 4;  // the cloud + one list per wave
+  UNOPOSE_REQUIRE(lds <= 64 * 1024, "%s: N=%d nsample=%d exceed the 64 KiB LDS tile", what, N, nsample);
+  const long centres = (long)B * N;
+  const int cpw = centres >= 65536 ? 8 : centres >= 16384 ? 4 : centres >= 4096 ? 2 : 1;
+  hipLaunchKernelGGL(query_lrf_group_kernel<IDX>, dim3(cdiv(N, 4 * cpw), B), dim3(256), lds, (hipStream_t)stream, xyz, N, radius,
+                     nsample, cpw, out, new_xyz, idx);
+  return check_launch(what);
+}
 
 extern "C" {
 
@@ -440,31 +395,12 @@ int unopose_lrf_global(const float *pts, int B, int N, int use_ref_rad, float *o
 
 int unopose_query_lrf_group(const float *xyz, int B, int N, float radius, int nsample, float *out,
                             unopose_stream_t stream) {
-  UNOPOSE_REQUIRE(xyz && out, "query_lrf_group: null pointer");
-  UNOPOSE_REQUIRE(B >= 0 && N >= 1 && nsample >= 1 && B <= 65535, "query_lrf_group: bad sizes");
-  if (B == 0) return UNOPOSE_OK;
-  const size_t lds = ((size_t)3 * N + 4 * (size_t)nsample) * 4;
-  UNOPOSE_REQUIRE(lds <= 64 * 1024, "query_lrf_group: N=%d nsample=%d exceed the 64 KiB LDS tile", N, nsample);
-  const long centres = (long)B * N;
-  int cpw = centres >= 65536 ? 8 : centres >= 16384 ? 4 : centres >= 4096 ? 2 : 1;
-  dim3 grid(cdiv(N, 4 * cpw), B);
-  hipLaunchKernelGGL(query_lrf_group_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, xyz, N, radius, nsample, cpw,
-                     out, (const float *)nullptr, (const int *)nullptr);
-  return check_launch("query_lrf_group");
+  return launch_query_lrf_group<false>(xyz, nullptr, nullptr, B, N, radius, nsample, out, stream);
 }
 
 int unopose_lrf_group_idx(const float *xyz, const float *new_xyz, const int *idx, int B, int N, float radius, int nsample,
                           float *out, unopose_stream_t stream) {
-  UNOPOSE_REQUIRE(xyz && new_xyz && idx && out, "lrf_group_idx: null pointer");
-  UNOPOSE_REQUIRE(B >= 0 && N >= 1 && nsample >= 1 && B <= 65535, "lrf_group_idx: bad sizes");
-  if (B == 0) return UNOPOSE_OK;
-  const size_t lds = ((size_t)3 * N + 4 * (size_t)nsample) * 4;
-  UNOPOSE_REQUIRE(lds <= 64 * 1024, "lrf_group_idx: N=%d nsample=%d exceed the 64 KiB LDS tile", N, nsample);
-  const long centres = (long)B * N;
-  const int cpw = centres >= 65536 ? 8 : centres >= 16384 ? 4 : centres >= 4096 ? 2 : 1;
-  hipLaunchKernelGGL(query_lrf_group_kernel<true>, dim3(cdiv(N, 4 * cpw), B), dim3(256), lds, (hipStream_t)stream, xyz, N, radius,
-                     nsample, cpw, out, new_xyz, idx);
-  return check_launch("lrf_group_idx");
+  return launch_query_lrf_group<true>(xyz, new_xyz, idx, B, N, radius, nsample, out, stream);
 }
 
 int unopose_weighted_procrustes(const float *src, const float *ref, const float *w, int M, int N, float thresh,

@@ -14,197 +14,32 @@
 // max-pooled result reaches HBM.
 // That is the exact-fp32 kernel (pe_group_mlp_max_kernel).  The bf16 hi/lo-split form further down is two kernels: pe_geometry_kernel writes
 // the lists, counts and frames of one or both scales of a cloud, pe_group_mlp_max_bf16x3_kernel runs the MLP + max over them.
+// Neighbour list and frame are lrf.h's, the code geom.hip's query_lrf_group_kernel runs too; only the x axis' normalisation differs
+// (pe_frame_axes below).
 #include <algorithm>
 
 #include "common.h"
 #include "jacobi3.h"
+#include "lrf.h"
 
 namespace unopose {
-
-constexpr int PE_SCAN_STEPS = 4;  // 64-candidate steps of the ball query per loop trip (measured against 1 step per trip)
 
 // channel held by accumulator register r of half-wave h in the 32x32 C/D layout
 __device__ __forceinline__ int cd_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
-// Ball query (pointnet2 ball_query_gpu.cu:14-49 semantics) into the wave's LDS neighbour list and the
-// local reference frame of LRF_batch (pointnet2_utils.py:436-481) for one centre; wave-collective.
-// `cand` / `ncand`: optional list of candidate indices IN INDEX ORDER that is known to contain every point
-// within the radius (the neighbour list a larger-radius pass of the same cloud wrote, see cand_out below);
-// ncand < 0 = scan the whole cloud.  Returns the number of points inside the radius if the list holds them
-// all, a value > S otherwise.
-// ---- Round 5: a uniform grid for the ball query of the bf16x3 kernel.  The scan tests all N points of the cloud per centre although
-// ~75 of 2048 lie inside the radius; cells of edge >= 1.001 radius (at most PE_GDIM per axis: larger clouds get larger cells) leave the 27
-// cells around the centre's, and cell ids run along x, so those are NINE contiguous runs of the cell-sorted point list: ~9 steps of 64
-// candidates instead of 32.  The reference's order (the first S hits BY INDEX) is kept exactly: hits set bits of an N-bit map in LDS
-// (ds_or), and the list is read off the map in index order (popcount prefix over the lanes' words) -- same hit test on the same
-// coordinates, same list, bit-identical outputs.
+// The ball query's grid (LrfGrid, lrf.h) is built by pe_geometry_kernel: at most PE_GDIM cells per axis.
 constexpr int PE_GDIM = 8, PE_GCELLS = PE_GDIM * PE_GDIM * PE_GDIM;
-struct PeGrid {
-  float ox, oy, oz, ihx, ihy, ihz;  // origin, inverse cell edges
-  int nx, ny, nz;
-  const u16 *start;  // [PE_GCELLS + 1]: first slot of a cell in `order`
-  const u16 *order;  // [N] point ids sorted by cell
-  uint32_t *bits;    // this wave's map, ceil(N / 32) words
-};
-__device__ __forceinline__ int pe_cell(float v, float o, float ih, int n) { return max(0, min(n - 1, (int)((v - o) * ih))); }
 
-// The ball query alone: fills nbr[0..S) (padding included) and returns the count as described above.  `cand` may be a list in LDS
-// (the wide scale's list of the same centre, CT = u16) or in global memory (CT = int).
-template <typename NT, typename CT>
-__device__ __forceinline__ int pe_ball_query(const float *sx, const float *sy, const float *sz, int N, int S, float r2, int lane,
-                                             float cx, float cy, float cz, NT *nbr, const CT *cand, int ncand, const PeGrid &g, bool use_grid) {
-  // ---- ball query (pointnet2 ball_query_gpu.cu:14-49 semantics)
-  int cnt = 0, first = 0;
-  if (use_grid && ncand < 0) {
-    const int W = (N + 31) >> 5;
-    for (int w = lane; w < W; w += 64) g.bits[w] = 0u;
-    // the nine runs: lane i < 9 looks up run (dy, dz) = (i % 3 - 1, i / 3 - 1)
-    const int icx = pe_cell(cx, g.ox, g.ihx, g.nx), icy = pe_cell(cy, g.oy, g.ihy, g.ny),
-              icz = pe_cell(cz, g.oz, g.ihz, g.nz);
-    int rs = 0, re = 0;
-    if (lane < 9) {
-      const int y = icy + lane % 3 - 1, z = icz + lane / 3 - 1;
-      if (y >= 0 && y < g.ny && z >= 0 && z < g.nz) {
-        const int row = (z * g.ny + y) * g.nx;
-        rs = g.start[row + max(icx - 1, 0)];
-        re = g.start[row + min(icx + 1, g.nx - 1) + 1];
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll 1
-    for (int i = 0; i < 9; ++i) {
-      const int s0 = __builtin_amdgcn_readlane(rs, i), e0 = __builtin_amdgcn_readlane(re, i);
-      for (int q = s0 + lane; q < e0; q += 64) {
-        const int k = g.order[q];
-        const float x = sx[k], y = sy[k], z = sz[k];
-        const float d2 = (cx - x) * (cx - x) + (cy - y) * (cy - y) + (cz - z) * (cz - z);
-        if (d2 < r2) atomicOr(&g.bits[k >> 5], 1u << (k & 31));
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // the list in index order: lane-owned words, exclusive prefix of their popcounts
-    for (int w0 = 0; w0 < W; w0 += 64) {
-      const int w = w0 + lane;
-      uint32_t bits = w < W ? g.bits[w] : 0u;
-      const int pc = __builtin_popcount(bits);
-      int incl = pc;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-      }
-      int pos = cnt + incl - pc;
-      while (bits) {
-        const int bpos = __builtin_ctz(bits);
-        bits &= bits - 1u;
-        if (pos < S) nbr[pos] = (NT)(32 * w + bpos);
-        ++pos;
-      }
-      cnt += __builtin_amdgcn_readlane(incl, 63);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (cnt > 0) first = nbr[0];
-  } else {
-  const int nscan = ncand >= 0 ? ncand : N;
-  int k0 = 0;
-  // PE_SCAN_STEPS (four) 64-candidate steps per trip: their LDS reads, distance tests and ballots are independent, only the list positions chain
-  // through cnt (one step at a time the loop was a chain of LDS -> VALU -> ballot -> scalar latencies: a third of a launch)
-  constexpr int U = PE_SCAN_STEPS;
-  for (; k0 < nscan && cnt < S; k0 += 64 * U) {
-    int kk[U];
-    unsigned long long mask[U];
-    bool hit[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      int k = k0 + 64 * u + lane;
-      hit[u] = false;
-      if (k < nscan) {
-        if (ncand >= 0) k = cand[k];
-        const float x = sx[k], y = sy[k], z = sz[k];
-        const float d2 = (cx - x) * (cx - x) + (cy - y) * (cy - y) + (cz - z) * (cz - z);
-        hit[u] = d2 < r2;
-      }
-      kk[u] = k;
-      mask[u] = __ballot(hit[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (mask[u]) {
-        const int pre =
-            (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask[u], 0u));
-        const int pos = cnt + pre;
-        if (hit[u] && pos < S) nbr[pos] = (NT)kk[u];
-        if (cnt == 0) {
-          const int fl = __builtin_ctzll(mask[u]);  // lane of the first hit
-          first = ncand >= 0 ? __builtin_amdgcn_readlane(kk[u], fl) : k0 + 64 * u + fl;
-        }
-        cnt += __builtin_popcountll(mask[u]);
-      }
-    }
-  }
-  if (k0 < nscan) cnt = S + 1;  // stopped early at a full list: the rest of the cloud was not looked at
-  }
-  for (int l = min(cnt, S) + lane; l < S; l += 64) nbr[l] = (NT)first;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  return cnt;
-}
-
-// ---- local reference frame (LRF_batch, pointnet2_utils.py:436-481) in three wave-collective pieces: the covariance of the list,
-// the eigen-solve (eig_sym3: per centre in the fp32 kernel, one centre per LANE in the geometry kernel), the sign vote and x axis.
-// (measured and not kept, round 5: the three passes with the padding entries' terms as per-pass constants -- bit-identical, no faster:
-//  the frame's time is the eigen-solver and the wave reductions, not these reads)
-template <typename NT>
-__device__ __forceinline__ void pe_covariance(const float *sx, const float *sy, const float *sz, int S, int lane, float cx, float cy,
-                                              float cz, const NT *nbr, float &a00, float &a01, float &a02, float &a11, float &a12,
-                                              float &a22) {
-  a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0;
-  for (int l = lane; l < S; l += 64) {
-    const int k = nbr[l];
-    const float x = cx - sx[k], y = cy - sy[k], z = cz - sz[k];
-    a00 += x * x; a01 += x * y; a02 += x * z; a11 += y * y; a12 += y * z; a22 += z * z;
-  }
-  const float inv_s = 1.f / (float)S;
-  a00 = wave_sum_f32(a00) * inv_s; a01 = wave_sum_f32(a01) * inv_s; a02 = wave_sum_f32(a02) * inv_s;
-  a11 = wave_sum_f32(a11) * inv_s; a12 = wave_sum_f32(a12) * inv_s; a22 = wave_sum_f32(a22) * inv_s;
-}
-
-// z0: the eigenvector of the smallest eigenvalue of the covariance (wave-uniform)
+// The frame of one centre from z0, the eigenvector of the smallest eigenvalue of the covariance (wave-uniform).
 template <typename NT>
 __device__ __forceinline__ void pe_frame_axes(const float *sx, const float *sy, const float *sz, int S, float radius, int lane,
                                               float cx, float cy, float cz, const NT *nbr, Vec3 z0, Vec3 &xp, Vec3 &yp, Vec3 &zp) {
-  int vote = 0;
-  for (int l0i = 0; l0i < S; l0i += 64) {
-    const int l = l0i + lane;
-    float pr = 0.f;
-    if (l < S) {
-      const int k = nbr[l];
-      pr = z0.x * (cx - sx[k]) + z0.y * (cy - sy[k]) + z0.z * (cz - sz[k]);
-    }
-    vote += __builtin_popcountll(__ballot(pr > 1e-3f)) - __builtin_popcountll(__ballot(pr < -1e-3f));
-  }
-  zp = vote < 0 ? scale(z0, -1.f) : z0;
-  float vx = 0, vy = 0, vz = 0;
-  for (int l = lane; l < S; l += 64) {
-    const int k = nbr[l];
-    const Vec3 xn = v3(sx[k] - cx, sy[k] - cy, sz[k] - cz);
-    const float nrm = dot(zp, xn);
-    const Vec3 vi = sub(xn, scale(zp, nrm));
-    float alpha = radius - sqrtf(dot(xn, xn));
-    alpha *= alpha;
-    const float ab = alpha * (nrm * nrm);
-    vx += ab * vi.x; vy += ab * vi.y; vz += ab * vi.z;
-  }
-  vx = wave_sum_f32(vx); vy = wave_sum_f32(vy); vz = wave_sum_f32(vz);
-  const float nacc = sqrtf(vx * vx + vy * vy + vz * vz) + 1e-10f;
-  xp = v3(vx / nacc, vy / nacc, vz / nacc);
+  Vec3 acc;
+  lrf_vote_xacc(sx, sy, sz, S, radius, lane, cx, cy, cz, nbr, z0, zp, acc);
+  // x = acc / (|acc| + 1e-10) by DIVISION here, by multiplication with the reciprocal in geom.hip's finish_frame: the two forms differ
+  // in the last bit.  Each is kept because the outputs of its kernels are pinned (bit-identity records under profiles/).
+  const float nacc = sqrtf(acc.x * acc.x + acc.y * acc.y + acc.z * acc.z) + 1e-10f;
+  xp = v3(acc.x / nacc, acc.y / nacc, acc.z / nacc);
   yp = cross(xp, zp);
 }
 
@@ -213,14 +48,25 @@ template <typename NT>
 __device__ __forceinline__ int pe_centre_frame(const float *sx, const float *sy, const float *sz, int N, int S,
                                                float radius, float r2, int lane, float cx, float cy, float cz,
                                                NT *nbr, Vec3 &xp, Vec3 &yp, Vec3 &zp) {
-  const int cnt = pe_ball_query<NT, int>(sx, sy, sz, N, S, r2, lane, cx, cy, cz, nbr, nullptr, -1, PeGrid{}, false);
+  const int cnt = lrf_ball_query<NT, int>(sx, sy, sz, N, S, r2, lane, cx, cy, cz, nbr, nullptr, -1, LrfGrid{}, false);
   float a00, a01, a02, a11, a12, a22;
-  pe_covariance(sx, sy, sz, S, lane, cx, cy, cz, nbr, a00, a01, a02, a11, a12, a22);
+  lrf_covariance(sx, sy, sz, S, lane, cx, cy, cz, nbr, a00, a01, a02, a11, a12, a22);
   Vec3 e0, e1, z0;
   float l0, l1, l2;
   eig_sym3(a00, a01, a02, a11, a12, a22, e0, e1, z0, l0, l1, l2);
   pe_frame_axes(sx, sy, sz, S, radius, lane, cx, cy, cz, nbr, z0, xp, yp, zp);
   return cnt;
+}
+
+// The max-pool's last step for one accumulator register: the maximum over the 32 neighbour lanes of each half-wave (lanes 31 / 63
+// hold it) goes to the stage slot of the register's channel.
+__device__ __forceinline__ void pe_pool_neighbours(float v, float *slot, int col) {
+  v = fmaxf(v, dpp_f32<0x111, 0xF>(v, 0.f));
+  v = fmaxf(v, dpp_f32<0x112, 0xF>(v, 0.f));
+  v = fmaxf(v, dpp_f32<0x114, 0xF>(v, 0.f));
+  v = fmaxf(v, dpp_f32<0x118, 0xF>(v, 0.f));
+  v = fmaxf(v, dpp_f32<0x142, 0xA>(v, 0.f));  // row_bcast:15 into rows 1 and 3
+  if (col == 31) *slot = v;
 }
 
 struct PeLds {
@@ -247,11 +93,7 @@ __global__ __launch_bounds__(256) void pe_group_mlp_max_kernel(
   float *stage = stage_all + wave * 128;
   const float *P = xyz + (size_t)b * N * 3;
 
-  for (int e = tid; e < N * 3; e += 256) {
-    const float v = P[e];
-    const int p = e / 3, comp = e - p * 3;
-    (comp == 0 ? sx : comp == 1 ? sy : sz)[p] = v;
-  }
+  for (int e = tid; e < N * 3; e += 256) lrf_stage_coord(sx, sy, sz, e, P[e]);
   // weights arrive row-major [out][in] (BN already folded): transpose to [in][out]
   for (int e = tid; e < 32 * 6; e += 256) L->w1[(e % 6) * 32 + e / 6] = w1[e];
   for (int e = tid; e < 64 * 32; e += 256) L->w2[(e % 32) * 64 + e / 32] = w2[e];
@@ -323,22 +165,11 @@ __global__ __launch_bounds__(256) void pe_group_mlp_max_kernel(
           rmax[ot][r] = fmaxf(rmax[ot][r], fmaxf(h3[r] + L->b3[ot * 32 + cd_row(r, half)], 0.f));
       }
     }
-    // ---- max over the 32 neighbour lanes of each half-wave; lanes 31 / 63 hold the result
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float v = rmax[t][r];
-        v = fmaxf(v, dpp_f32<0x111, 0xF>(v, 0.f));
-        v = fmaxf(v, dpp_f32<0x112, 0xF>(v, 0.f));
-        v = fmaxf(v, dpp_f32<0x114, 0xF>(v, 0.f));
-        v = fmaxf(v, dpp_f32<0x118, 0xF>(v, 0.f));
-        v = fmaxf(v, dpp_f32<0x142, 0xA>(v, 0.f));  // row_bcast:15 into rows 1 and 3
-        if (col == 31) stage[t * 32 + cd_row(r, half)] = v;
-      }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int r = 0; r < 16; ++r) pe_pool_neighbours(rmax[t][r], &stage[t * 32 + cd_row(r, half)], col);
+    wave_lds_handover();
     float *O = out + ((size_t)b * N + j) * 128;
     O[lane] = stage[lane];
     O[lane + 64] = stage[lane + 64];
@@ -436,13 +267,9 @@ __global__ __launch_bounds__(PE_GW * 64) void pe_geometry_kernel(
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const float *P = xyz + (size_t)b * N * 3;
 
-  for (int e = tid; e < N * 3; e += PE_GW * 64) {
-    const float v = P[e];
-    const int p = e / 3, comp = e - p * 3;
-    (comp == 0 ? sx : comp == 1 ? sy : sz)[p] = v;
-  }
+  for (int e = tid; e < N * 3; e += PE_GW * 64) lrf_stage_coord(sx, sy, sz, e, P[e]);
   __syncthreads();
-  PeGrid grid = {};
+  LrfGrid grid = {};
   if (use_grid) {
     // ---- the cloud's grid (cells of the WIDE radius serve both scales: a cell edge only has to be >= the radius queried)
     float lo[3] = {3e38f, 3e38f, 3e38f}, hi[3] = {-3e38f, -3e38f, -3e38f};
@@ -478,8 +305,8 @@ __global__ __launch_bounds__(PE_GW * 64) void pe_geometry_kernel(
     grid.nx = nd[0], grid.ny = nd[1], grid.nz = nd[2];
     grid.start = gstart, grid.order = gorder, grid.bits = bits_all + wave * BW;
     auto cell_of = [&](int p) {
-      return (pe_cell(sz[p], grid.oz, grid.ihz, grid.nz) * grid.ny + pe_cell(sy[p], grid.oy, grid.ihy, grid.ny)) * grid.nx +
-             pe_cell(sx[p], grid.ox, grid.ihx, grid.nx);
+      return (lrf_cell(sz[p], grid.oz, grid.ihz, grid.nz) * grid.ny + lrf_cell(sy[p], grid.oy, grid.ihy, grid.ny)) * grid.nx +
+             lrf_cell(sx[p], grid.ox, grid.ihx, grid.nx);
     };
     for (int p = tid; p < N; p += PE_GW * 64) atomicAdd(&cnt32[cell_of(p)], 1u);
     __syncthreads();
@@ -526,7 +353,7 @@ __global__ __launch_bounds__(PE_GW * 64) void pe_geometry_kernel(
         ncand = cand_cnt_in[row];  // -1: the producer's list overflowed, scan everything
         cand = cand_in + row * cand_stride;
       }
-      const int c = pe_ball_query<u16, int>(sx, sy, sz, N, S0, r2_0, lane, cx, cy, cz, n0, cand, ncand, grid, use_grid != 0);
+      const int c = lrf_ball_query<u16, int>(sx, sy, sz, N, S0, r2_0, lane, cx, cy, cz, n0, cand, ncand, grid, use_grid != 0);
       {
         uint32_t *dst = reinterpret_cast<uint32_t *>(lists0 + row * S0);
         const uint32_t *src = reinterpret_cast<const uint32_t *>(n0);
@@ -538,16 +365,16 @@ __global__ __launch_bounds__(PE_GW * 64) void pe_geometry_kernel(
         if (lane == 0) cnt0[row] = c <= S0 ? c : -1;
       }
       float a00, a01, a02, a11, a12, a22;
-      pe_covariance(sx, sy, sz, S0, lane, cx, cy, cz, n0, a00, a01, a02, a11, a12, a22);
+      lrf_covariance(sx, sy, sz, S0, lane, cx, cy, cz, n0, a00, a01, a02, a11, a12, a22);
       if (lane == i) m00 = a00, m01 = a01, m02 = a02, m11 = a11, m12 = a12, m22 = a22;
       if (S1) {
         // the narrow scale tests the wide list's points (all of them lie in it) unless that list overflowed
-        const int c1 = pe_ball_query<u16, u16>(sx, sy, sz, N, S1, r2_1, lane, cx, cy, cz, n1, n0, c <= S0 ? c : -1, grid, use_grid != 0);
+        const int c1 = lrf_ball_query<u16, u16>(sx, sy, sz, N, S1, r2_1, lane, cx, cy, cz, n1, n0, c <= S0 ? c : -1, grid, use_grid != 0);
         uint32_t *dst = reinterpret_cast<uint32_t *>(lists1 + row * S1);
         const uint32_t *src = reinterpret_cast<const uint32_t *>(n1);
         for (int l = lane; l < (S1 >> 1); l += 64) dst[l] = src[l];
         if (lane == 0) cnt1[row] = c1 <= S1 ? c1 : -1;
-        pe_covariance(sx, sy, sz, S1, lane, cx, cy, cz, n1, a00, a01, a02, a11, a12, a22);
+        lrf_covariance(sx, sy, sz, S1, lane, cx, cy, cz, n1, a00, a01, a02, a11, a12, a22);
         if (lane == PE_GB + i) m00 = a00, m01 = a01, m02 = a02, m11 = a11, m12 = a12, m22 = a22;
       }
     }
@@ -608,11 +435,7 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
   const int j0 = (blockIdx.x * PE_NW + wave) * cpw;
   if (j0 < N) fetch(j0);
 
-  for (int e = tid; e < N * 3; e += PE_NW * 64) {
-    const float v = P[e];
-    const int p = e / 3, comp = e - p * 3;
-    (comp == 0 ? sx : comp == 1 ? sy : sz)[p] = v;
-  }
+  for (int e = tid; e < N * 3; e += PE_NW * 64) lrf_stage_coord(sx, sy, sz, e, P[e]);
   // the LDS weight image (hi/lo bf16, permuted, swizzled; built once by pe_pack_weights_kernel) is copied
   // verbatim with coalesced 16-byte loads
   for (int e = tid; e < (int)(sizeof(PeLdsB) / 16); e += PE_NW * 64) smem4[e] = *reinterpret_cast<const float4 *>(image + e);
@@ -633,9 +456,7 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
     const Vec3 zp = v3(pe_readlane_f32(pf, 6), pe_readlane_f32(pf, 7), pe_readlane_f32(pf, 8));
     const int cnt_in = __builtin_amdgcn_readlane(__float_as_int(pf), 9);
     const int cnt = cnt_in < 0 ? S + 1 : cnt_in;  // -1: more points inside the radius than the list holds
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handover();
     if (ci + 1 < cpw && j + 1 < N) fetch(j + 1);
 
     f32x16 rmax[4];
@@ -758,18 +579,8 @@ __global__ __launch_bounds__(PE_NW * 64, 8 / PE_NW) void pe_group_mlp_max_bf16x3
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float v = rmax[t][r];
-        v = fmaxf(v, dpp_f32<0x111, 0xF>(v, 0.f));
-        v = fmaxf(v, dpp_f32<0x112, 0xF>(v, 0.f));
-        v = fmaxf(v, dpp_f32<0x114, 0xF>(v, 0.f));
-        v = fmaxf(v, dpp_f32<0x118, 0xF>(v, 0.f));
-        v = fmaxf(v, dpp_f32<0x142, 0xA>(v, 0.f));
-        if (col == 31) stage[t * 32 + cd_row(r, half)] = v;
-      }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int r = 0; r < 16; ++r) pe_pool_neighbours(rmax[t][r], &stage[t * 32 + cd_row(r, half)], col);
+    wave_lds_handover();
     float *O = out + ((size_t)b * N + j) * out_ld;
     if (!out_split) {
       O[lane] = stage[lane];
