@@ -323,7 +323,8 @@ def compute_coarse_rt_overlap(atten, score, pts1, pts2, rand, n1p=6000, n2p=300,
     B, N1, _ = pts1.shape
     N2 = pts2.shape[1]
     atten, pts1, pts2 = atten.float(), pts1.float(), pts2.float()
-    a, l1, l2 = _soft_assignment(atten, score[:, :N1].float(), score[:, N2:].float())
+    # the reference's `N2:` (U:440) is defined for N1 == N2 only; `N1:` is the same slice there
+    a, l1, l2 = _soft_assignment(atten, score[:, :N1].float(), score[:, N1:].float())
     w1, w2 = (l1 > 0).float(), (l2 > 0).float()
     ps = a[:, 1:, 1:] * w1.unsqueeze(2) * w2.unsqueeze(1)
     ps = ps.reshape(B, N1 * N2) ** 1.5

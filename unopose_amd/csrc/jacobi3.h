@@ -144,9 +144,18 @@ __device__ __forceinline__ void kabsch_from_H(const float h[9], float R[9]) {
   }
   Vec3 g1o = sub(g1, scale(u0, dot(g1, u0)));
   const float n1 = dot(g1o, g1o);
-  if (n1 > 1e-24f * s0 && n1 > 0.f) {
+  bool rank2 = n1 > 1e-24f * s0 && n1 > 0.f;
+  if (rank2) {
     u1 = scale(g1o, 1.f / sqrtf(n1));
-  } else {  // rank <= 1: any unit vector orthogonal to u0 (deterministic choice)
+    // second Gram-Schmidt pass: where H is rank 1 up to rounding (a hypothesis that drew one pair twice), g1 is noise that
+    // may lie along u0, and the one subtraction above leaves u1 . u0 at ~1e-7 |g1| / |g1o| (2e-4 seen), so R was no rotation.
+    // A unit u1 that loses half its length here was nothing but that noise: rank 1.
+    u1 = sub(u1, scale(u0, dot(u1, u0)));
+    const float n1b = dot(u1, u1);
+    rank2 = n1b > 0.25f;
+    if (rank2) u1 = scale(u1, 1.f / sqrtf(n1b));
+  }
+  if (!rank2) {  // rank <= 1: any unit vector orthogonal to u0 (deterministic choice)
     Vec3 a = fabsf(u0.x) < 0.9f ? v3(1, 0, 0) : v3(0, 1, 0);
     if (s0 <= 0.f) a = v3(0, 1, 0);
     Vec3 p = sub(a, scale(u0, dot(a, u0)));

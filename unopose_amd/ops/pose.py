@@ -118,13 +118,19 @@ def soft_assignment(atten, score1, score2):
     return a, label1, label2
 
 
+def _check_score_width(score, N1, N2):
+    if score.dim() != 2 or score.shape[1] != N1 + N2:
+        raise ValueError(f"score must be (B, N1 + N2) = (B, {N1 + N2}): the overlap scores of both clouds, got {tuple(score.shape)}")
+
+
 def coarse_pose_torch(atten, score, pts1, pts2, rand, n1p=6000, n2p=300):
     """compute_coarse_Rt_overlap (model_utils.py:411-490); `rand` (B,3*n1p) is the uniform draw the
     reference makes inside forward (:462).  [torch composite + HIP 3-point Procrustes]"""
     B, N1, _ = pts1.shape
     N2 = pts2.shape[1]
+    _check_score_width(score, N1, N2)
     atten, pts1, pts2 = atten.float(), pts1.float(), pts2.float()
-    a, l1, l2 = soft_assignment(atten, score[:, :N1].float(), score[:, N2:].float())
+    a, l1, l2 = soft_assignment(atten, score[:, :N1].float(), score[:, N1:].float())  # the reference's `N2:` (model_utils.py:440) is defined for N1 == N2 only
     w1, w2 = (l1 > 0).float(), (l2 > 0).float()
     ps = (a[:, 1:, 1:] * w1.unsqueeze(2) * w2.unsqueeze(1)).reshape(B, N1 * N2) ** 1.5
     # torch's CPU cumsum accumulates float32 input in double; mirror that so searchsorted agrees
@@ -184,9 +190,10 @@ def coarse_pose(atten, score, pts1, pts2, rand, n1p=6000, n2p=300):
     counting), candidate scoring, pick of the best candidate (`USE_OWN_TOPK`; off: torch.topk / max / gather)."""
     B, N1, _ = pts1.shape
     N2 = pts2.shape[1]
+    _check_score_width(score, N1, N2)
     atten, pts1, pts2 = _c(atten.float()), _c(pts1.float()), _c(pts2.float())
     check_f32(atten, "atten")
-    score1, score2 = _c(score[:, :N1].float()), _c(score[:, N2:].float())  # NB `N2:` (model_utils.py:440)
+    score1, score2 = _c(score[:, :N1].float()), _c(score[:, N1:].float())  # the reference's `N2:` (model_utils.py:440) is defined for N1 == N2 only
     rand = _c(rand.float())
     dev = atten.device
     with on_device(dev):
