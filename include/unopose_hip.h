@@ -662,6 +662,25 @@ int unopose_vsd_counts(const float *test, int n_test, const float *gt, int n_gt,
 int unopose_pose_errors(const double *pts, int n, const double *syms, int S, const double *est, const double *gt, const double *K, int P,
                         double *mssd, double *mspd, unopose_stream_t stream);
 
+/* The further pose errors of the evaluation for P (estimate, ground truth) pairs of ONE object per launch (csrc/posemetrics.hip;
+ * unopose_amd/bop_eval.py's add / adi / proj / re / te / proj_sym / re_sym / te_sym are the specification, i.e. lib/pysixd/pose_error.py:182-216,
+ * 255-295, 357-443).  All float64; the kernels assume finite poses and trust their sizes (the Python wrappers check on the host).
+ * _pose_metrics: pts (n,3) model points; syms (S,12) = row-major R then t of each symmetry (identity included); est, gt (P,12) poses laid
+ *     out the same way; K (P,9) row-major intrinsics -> out (7,P): rows add (mean 3-D displacement, model units), proj (mean displacement
+ *     of the projections, px), re (degrees: arccos of the clamped 0.5 (trace(R_e R_g^T) - 1)), te (|t_g - t_e|), then projS, reS, teS = the
+ *     minimum over the symmetries with the ground truth composed as R_g S_R, R_g S_t + t_g.  Fixed reduction tree: bit-reproducible.
+ *     proj_sym = 0 leaves the points x symmetries pass out and writes NaN into the projS row; with the identity as the only symmetry projS
+ *     is proj's value.
+ * _adi: pts (n,3), est, gt (P,12) -> adi (P) = mean over the points p of min over q of |(R_g p + t_g) - (R_e q + t_e)|, brute force over
+ *     LDS tiles of unopose_adi_tile_points() transformed points, a pair split into ceil(n / unopose_adi_slab_points()) workgroups whose
+ *     partial sums go to workspace (P * that many float64, device memory) and are added in index order.  n <= 2^24, P <= 65535. */
+int unopose_adi_tile_points(void);
+int unopose_adi_slab_points(void);
+int unopose_pose_metrics(const double *pts, int n, const double *syms, int S, const double *est, const double *gt, const double *K, int P,
+                         int proj_sym, double *out, unopose_stream_t stream);
+int unopose_adi(const double *pts, int n, const double *est, const double *gt, int P, double *workspace, double *adi,
+                unopose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

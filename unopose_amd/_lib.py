@@ -130,6 +130,10 @@ SIGNATURES = {
     "unopose_vsd_count_ints": [],
     "unopose_vsd_counts": [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "unopose_pose_errors": [_P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P],
+    "unopose_adi_tile_points": [],
+    "unopose_adi_slab_points": [],
+    "unopose_pose_metrics": [_P, _I, _P, _I, _P, _P, _P, _I, _I, _P, _P],
+    "unopose_adi": [_P, _I, _P, _P, _I, _P, _P, _P],
 }
 
 

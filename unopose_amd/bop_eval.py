@@ -15,7 +15,16 @@ Two routes to the same numbers: the host route (numpy per estimate; only the ras
 `average_recall(..., device=...)`, the device route: depth maps stay on the GPU and csrc/bopscore.hip turns them into the integer counts
 of `vsd` and the `mssd` / `mspd` distances for many pairs per launch; the matching and the recall averaging are the same host code.
 `load_dataset` reads a BOP dataset folder for scoring (own PLY reader, symmetries as the toolkit lists them, targets file) and
-`score_csv` ties it to a result file, as the reference's test run does after saving (`--eval` of unopose_amd.cli)."""
+`score_csv` ties it to a result file, as the reference's test run does after saving (`--eval` of unopose_amd.cli).
+
+Beyond BOP'19, `average_recall(..., error_types=...)` scores the error types of the reference's own script
+(`lib/pysixd/scripts/eval_pose_results_more.py:41-156`): `add, adi, ad, ABSadd, ABSadi, ABSad, AUCadd, AUCadi, AUCad, re, te, rete, proj, reS, teS,
+reteS, projS` -- `ERROR_TYPES` holds their thresholds, units and normalisation, `add, adi, proj, re, te, proj_sym, re_sym, te_sym` are the host
+functions (`lib/pysixd/pose_error.py`), csrc/posemetrics.hip the device route (`ops.pose_metrics`, `ops.adi`), and every such type adds a
+block with per-object recalls under `out["errors"]`.  The mask-overlap error `cus` and the other mask / bounding-box errors stay out.
+A deliberate difference: which objects take ADI under `ad / ABSad / AUCad` is not read from per-dataset id tables
+(`lib/pysixd/dataset_params.py:96-130`) but from the models -- an object whose `models_info.json` entry lists a discrete or continuous
+symmetry -- unless `symmetric_obj_ids=` (config key `bop_eval.symmetric_obj_ids`) says otherwise; the ids used are written with the scores."""
 import json
 import os.path as osp
 
@@ -73,6 +82,321 @@ def mspd(R_est, t_est, R_gt, t_gt, K, pts, syms):
     Rg, tg = _sym_poses(R_gt, t_gt.reshape(3), syms)
     gt = _project(np.einsum("sij,nj->sni", Rg, pts) + tg[:, None, :], K)
     return float(np.linalg.norm(gt - est[None], axis=2).max(axis=1).min())
+
+
+# ---- the further error types of lib/pysixd/scripts/eval_pose_results_more.py ----------------------------------------------------------
+DEFAULT_ERROR_TYPES = ("vsd", "mssd", "mspd")
+_AD_TH, _ABS_TH, _RT_TH = [[0.02], [0.05], [0.1]], [[2.0]], [[2.0], [5.0], [10.0]]
+_AUC_TH = [[float(th)] for th in np.linspace(10 / 10, 10, num=10)]
+
+
+def _etype(elements, thresholds, by_diameter=False, sphere_rule=False, cm=False, auc=False):
+    return dict(elements=elements, thresholds=thresholds, by_diameter=by_diameter, sphere_rule=sphere_rule, cm=cm, auc=auc)
+
+
+# type -> elements: the errors that make it up ("ad" = "adi" for a symmetric object, else "add"; `rete` carries two);
+#   thresholds: one list per correctness setting, one value per element (eval_pose_results_more.py:74-155);
+#   by_diameter: divided by the object diameter before thresholding (eval_calc_scores.py:70);
+#   sphere_rule: inf when |t_e - t_g| >= diameter, the spheres around the two poses do not overlap (eval_calc_errors.py:367-426);
+#   cm: every element in mm is divided by 10 (ABS*, AUC*; eval_calc_errors.py:473-527) -- "te" / "teS" elements always are (:569-591);
+#   auc: an area-under-curve metric, tabulated as the mean over its thresholds (bop_eval_utils.py:191-194).
+ERROR_TYPES = {
+    "add": _etype(("add",), _AD_TH, by_diameter=True, sphere_rule=True), "adi": _etype(("adi",), _AD_TH, by_diameter=True, sphere_rule=True),
+    "ad": _etype(("ad",), _AD_TH, by_diameter=True, sphere_rule=True),
+    "ABSadd": _etype(("add",), _ABS_TH, cm=True), "ABSadi": _etype(("adi",), _ABS_TH, cm=True), "ABSad": _etype(("ad",), _ABS_TH, cm=True),
+    "AUCadd": _etype(("add",), _AUC_TH, cm=True, auc=True), "AUCadi": _etype(("adi",), _AUC_TH, cm=True, auc=True),
+    "AUCad": _etype(("ad",), _AUC_TH, cm=True, auc=True),
+    "re": _etype(("re",), _RT_TH), "te": _etype(("te",), _RT_TH), "rete": _etype(("re", "te"), [[2.0, 2.0], [5.0, 5.0], [10.0, 10.0]]),
+    "proj": _etype(("proj",), _RT_TH),
+    "reS": _etype(("reS",), _RT_TH), "teS": _etype(("teS",), _RT_TH), "reteS": _etype(("reS", "teS"), [[2.0, 2.0], [5.0, 5.0], [10.0, 10.0]]),
+    "projS": _etype(("projS",), _RT_TH),
+}
+KNOWN_ERROR_TYPES = DEFAULT_ERROR_TYPES + tuple(ERROR_TYPES)
+ADI_CHUNK = 1 << 21  # distances the host `adi` forms at a time
+
+
+def parse_error_types(spec):
+    """`bop_eval.error_types` as the reference's `val_cfg` spells it -- a comma-separated string -- or a list / tuple -> tuple of names in
+    the order given, duplicates dropped; None = the BOP'19 three.  An unknown name is a ValueError that lists the known ones."""
+    if spec is None:
+        return DEFAULT_ERROR_TYPES
+    names = [n.strip() for n in spec.split(",")] if isinstance(spec, str) else [str(n).strip() for n in spec]
+    names = list(dict.fromkeys(n for n in names if n))
+    unknown = [n for n in names if n not in KNOWN_ERROR_TYPES]
+    if unknown or not names:
+        raise ValueError(f"bop_eval: unknown error type(s) {unknown} -- known: {', '.join(KNOWN_ERROR_TYPES)}")
+    return tuple(names)
+
+
+def add(R_est, t_est, R_gt, t_gt, pts):
+    """Average distance of the model points between the two poses (pose_error.py:255-270), model units."""
+    est, gt = pts @ R_est.T + t_est.reshape(1, 3), pts @ R_gt.T + t_gt.reshape(1, 3)
+    return float(np.linalg.norm(est - gt, axis=1).mean())
+
+
+def adi(R_est, t_est, R_gt, t_gt, pts, chunk=ADI_CHUNK):
+    """Average distance from each model point in the ground-truth pose to the NEAREST model point in the estimated pose
+    (pose_error.py:273-295, a KD-tree there): brute force in float64, `chunk` squared distances at a time formed per coordinate as
+    (dx^2 + dy^2) + dz^2, the sqrt after the min."""
+    est, gt = pts @ R_est.T + t_est.reshape(1, 3), pts @ R_gt.T + t_gt.reshape(1, 3)
+    rows, e = max(1, int(chunk) // len(pts)), np.ascontiguousarray(est.T)
+    near = []
+    for a in range(0, len(pts), rows):
+        g = gt[a:a + rows]
+        d2 = np.square(g[:, 0:1] - e[0][None])
+        d2 += np.square(g[:, 1:2] - e[1][None])
+        d2 += np.square(g[:, 2:3] - e[2][None])
+        near.append(np.sqrt(d2.min(axis=1)))
+    return float(np.concatenate(near).mean())
+
+
+def proj(R_est, t_est, R_gt, t_gt, K, pts):
+    """Average distance of the model points' projections, px (pose_error.py:438-443 `arp_2d`)."""
+    return float(np.linalg.norm(_project(pts @ R_est.T + t_est.reshape(1, 3), K) - _project(pts @ R_gt.T + t_gt.reshape(1, 3), K), axis=1).mean())
+
+
+def proj_sym(R_est, t_est, R_gt, t_gt, K, pts, syms):
+    """`proj`, the minimum over the object's symmetries (pose_error.py:182-192 `arp_2d_sym`)."""
+    est = _project(pts @ R_est.T + t_est.reshape(1, 3), K)
+    Rg, tg = _sym_poses(R_gt, t_gt.reshape(3), syms)
+    gt = _project(np.einsum("sij,nj->sni", Rg, pts) + tg[:, None, :], K)
+    return float(np.linalg.norm(gt - est[None], axis=2).mean(axis=1).min())
+
+
+def _composed_t(R_gt, t_gt, syms):
+    """R_gt S_t + t_gt of every symmetry, each sum in the fixed order ((a + b) + c) + t that csrc/posemetrics.hip keeps -> (S,3)."""
+    ts = np.stack([np.asarray(s["t"], np.float64).reshape(3) for s in syms])
+    Rg, tg = np.asarray(R_gt, np.float64), np.asarray(t_gt, np.float64).reshape(3)
+    return np.stack([Rg[r, 0] * ts[:, 0] + Rg[r, 1] * ts[:, 1] + Rg[r, 2] * ts[:, 2] + tg[r] for r in range(3)], axis=1)
+
+
+def _fma(a, b, c):
+    """a b + c with ONE rounding, elementwise on float64 arrays: numpy has no fused multiply-add, so the product is split exactly (Dekker),
+    added to c exactly (Knuth) and the two tails are added with rounding to odd, after which the last addition rounds as the fused
+    operation does (Boldo and Melquiond, "Emulation of a FMA and correctly rounded sums", 2008).  No overflow or underflow: the operands
+    here are entries of rotations."""
+    a, b, c = np.broadcast_arrays(np.asarray(a, np.float64), np.asarray(b, np.float64), np.asarray(c, np.float64))
+
+    def split(x):
+        t = 134217729.0 * x  # 2^27 + 1
+        hi = t - (t - x)
+        return hi, x - hi
+
+    def two_sum(x, y):
+        s = x + y
+        yy = s - x
+        return s, (x - (s - yy)) + (y - yy)
+
+    p = a * b
+    (ah, al), (bh, bl) = split(a), split(b)
+    pl = (((ah * bh - p) + ah * bl) + al * bh) + al * bl  # p + pl = a b exactly
+    th, tl = two_sum(c, p)
+    v, err = two_sum(tl, pl)
+    even = (np.asarray(v).view(np.int64) & 1) == 0
+    v = np.where((err != 0) & even, np.nextafter(v, np.where(err > 0, np.inf, -np.inf)), v)  # round to odd
+    return th + v
+
+
+def _dot3(a0, b0, a1, b1, a2, b2):
+    """One element of a 3 x 3 product in a fixed order: a0 b0 rounded, then two fused multiply-adds.  This is how the BLAS product of
+    pose_error.py:357-372 rounded when tests/golden/pose_metrics.json was recorded; written out, the value no longer depends on the BLAS
+    numpy was built with, and csrc/posemetrics.hip's dot3_blas is the same expression."""
+    return _fma(a2, b2, _fma(a1, b1, np.asarray(a0, np.float64) * np.asarray(b0, np.float64)))
+
+
+def _rotation_degrees(R_est, R):
+    """arccos of the clamped 0.5 (trace(R_est R^T) - 1) in degrees for R (..., 3, 3): the diagonal by `_dot3`, added in order."""
+    d = [_dot3(R_est[r, 0], R[..., r, 0], R_est[r, 1], R[..., r, 1], R_est[r, 2], R[..., r, 2]) for r in range(3)]
+    trace = np.minimum((d[0] + d[1]) + d[2], 3.0)
+    return np.rad2deg(np.arccos(np.clip(0.5 * (trace - 1.0), -1.0, 1.0)))
+
+
+def re(R_est, R_gt):
+    """Rotation error in degrees: arccos of the clamped 0.5 (trace(R_est R_gt^T) - 1) (pose_error.py:357-372).  Near 0 degrees the result
+    moves by 1e-6 degrees per ulp of the trace (an exact copy of a rotation scores 0 or ~2e-6), so the trace is formed by explicit
+    arithmetic in one fixed order (`_dot3`), which csrc/posemetrics.hip restates."""
+    return float(_rotation_degrees(np.asarray(R_est, np.float64).reshape(3, 3), np.asarray(R_gt, np.float64).reshape(3, 3)))
+
+
+def re_sym(R_est, R_gt, syms):
+    """`re` against R_gt S_R, the minimum over the object's symmetries (pose_error.py:375-394); R_gt S_R by `_dot3` too."""
+    Rg, Q = np.asarray(R_gt, np.float64).reshape(3, 3), np.stack([np.asarray(s["R"], np.float64).reshape(3, 3) for s in syms])
+    T = np.stack([np.stack([_dot3(Rg[r, 0], Q[:, 0, c], Rg[r, 1], Q[:, 1, c], Rg[r, 2], Q[:, 2, c]) for c in range(3)], axis=1) for r in range(3)], axis=1)
+    return float(_rotation_degrees(np.asarray(R_est, np.float64).reshape(3, 3), T).min())
+
+
+def te(t_est, t_gt):
+    """Translation error |t_gt - t_est| in model units (pose_error.py:404-415)."""
+    d = np.asarray(t_gt, np.float64).reshape(3) - np.asarray(t_est, np.float64).reshape(3)
+    return float(np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]))
+
+
+def te_sym(t_est, t_gt, R_gt, syms):
+    """`te`, the minimum over the object's symmetries: |R_gt S_t + t_gt - t_est| (pose_error.py:418-435)."""
+    d = _composed_t(R_gt, t_gt, syms) - np.asarray(t_est, np.float64).reshape(1, 3)
+    return float(np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]).min()))
+
+
+def default_symmetric_obj_ids(models):
+    """The objects that take ADI under `ad / ABSad / AUCad`: those whose symmetry list holds more than the identity."""
+    return sorted(o for o, m in models.items() if len(m["symmetries"]) > 1)
+
+
+def _bases(types, symmetric):
+    """The errors an object's pairs need for `types`."""
+    out = set()
+    for T in types:
+        if T in ERROR_TYPES:
+            out.update(("adi" if symmetric else "add") if e == "ad" else e for e in ERROR_TYPES[T]["elements"])
+    return out
+
+
+def _adi_wanted(types, symmetric, apart):
+    """Does a pair need its ADI?  `apart`: the sphere rule holds (|t_e - t_g| >= diameter), so the types under it are inf without it."""
+    return any("adi" in _bases((T,), symmetric) and not (ERROR_TYPES[T]["sphere_rule"] and apart) for T in types if T in ERROR_TYPES)
+
+
+def metric_pairs(walk, models, types, symmetric_obj_ids):
+    """The pairs the further error types are computed for -> [dict(key, r, g, K, obj_id, apart, bases)], keys as `scored_pairs` documents
+    them.  The sphere rule is decided here, on the host, from |t_e - t_g| and the diameter: a pair under it is not handed to ADI."""
+    out = []
+    for sid, iid, K, obj_id, rows, mine in scored_pairs(walk):
+        sym = obj_id in symmetric_obj_ids
+        for rank, r in enumerate(rows):
+            for gid, g in mine:
+                apart = not (np.linalg.norm(np.asarray(r["t"], np.float64).reshape(3) - np.asarray(g["t"], np.float64).reshape(3)) < models[obj_id]["diameter"])
+                bases = _bases(types, sym)
+                if "adi" in bases and not _adi_wanted(types, sym, apart):
+                    bases = bases - {"adi"}
+                out.append(dict(key=(sid, iid, obj_id, rank, gid), r=r, g=g, K=K, obj_id=obj_id, apart=apart, bases=bases))
+    return out
+
+
+def host_pose_metrics(pairs, models):
+    """The errors each pair needs, with the host functions -> {key: {name: value}}."""
+    out = {}
+    for p in pairs:
+        m, (Re, te_), (Rg, tg) = models[p["obj_id"]], (np.asarray(p["r"]["R"], np.float64), np.asarray(p["r"]["t"], np.float64)), \
+            (np.asarray(p["g"]["R"], np.float64), np.asarray(p["g"]["t"], np.float64))
+        if not (np.isfinite(Re).all() and np.isfinite(te_).all() and np.isfinite(Rg).all() and np.isfinite(tg).all()):
+            out[p["key"]] = {b: float("nan") for b in p["bases"]}
+            continue
+        fn = dict(add=lambda: add(Re, te_, Rg, tg, m["pts"]), adi=lambda: adi(Re, te_, Rg, tg, m["pts"]), proj=lambda: proj(Re, te_, Rg, tg, p["K"], m["pts"]),
+                  re=lambda: re(Re, Rg), te=lambda: te(te_, tg), projS=lambda: proj_sym(Re, te_, Rg, tg, p["K"], m["pts"], m["symmetries"]),
+                  reS=lambda: re_sym(Re, Rg, m["symmetries"]), teS=lambda: te_sym(te_, tg, Rg, m["symmetries"]))
+        out[p["key"]] = {b: fn[b]() for b in p["bases"]}
+    return out
+
+
+def device_pose_metrics(pairs, models, device):
+    """`host_pose_metrics` on the device: one `ops.pose_metrics` launch per object (with the identity alone where no symmetry-aware error is
+    asked for, and without the projS pass where projS is not) plus `ops.adi` for the pairs that need ADI, everything queued before the
+    first read-back -> {key: {name: value}}."""
+    from .ops.score import adi as adi_op, pose_metrics
+
+    dev = _cuda_device(device)
+    by_obj = {}
+    for p in pairs:
+        by_obj.setdefault(p["obj_id"], []).append(p)
+    pending = []
+    for obj_id, group in by_obj.items():
+        m = models[obj_id]
+        poses = lambda g: ([p["r"]["R"] for p in g], [p["r"]["t"] for p in g], [p["g"]["R"] for p in g], [p["g"]["t"] for p in g])  # noqa: E731
+        several = [p for p in group if p["bases"] - {"adi"}]
+        if several:
+            syms = m["symmetries"] if any(p["bases"] & {"projS", "reS", "teS"} for p in several) else [dict(R=np.eye(3), t=np.zeros(3))]
+            proj_sym = any("projS" in p["bases"] for p in several)  # reS / teS alone do not pay for points x symmetries projections
+            pending.append((several, None, pose_metrics(m["pts"], syms, *poses(several), [p["K"] for p in several], dev, proj_sym=proj_sym)))
+        nearest = [p for p in group if "adi" in p["bases"]]
+        for a in range(0, len(nearest), 65535):  # the launch limit of pairs
+            pending.append((nearest[a:a + 65535], "adi", adi_op(m["pts"], *poses(nearest[a:a + 65535]), dev)))
+    out = {p["key"]: {} for p in pairs}
+    for group, name, res in pending:  # read back after everything is queued
+        cols = {name: res.cpu().numpy()} if name else {k: v.cpu().numpy() for k, v in res.items()}
+        for i, p in enumerate(group):
+            out[p["key"]].update({b: float(cols[b][i]) for b in p["bases"] if b in cols})
+    return out
+
+
+def pair_error(T, values, diameter, symmetric, apart):
+    """The error elements of type `T` for one pair, as eval_calc_errors.py stores and eval_calc_scores.py normalises them: list of floats."""
+    spec = ERROR_TYPES[T]
+    if spec["sphere_rule"] and apart:
+        return [float("inf")]
+    out = []
+    for e in spec["elements"]:
+        e = ("adi" if symmetric else "add") if e == "ad" else e
+        v = values[e]
+        if spec["cm"] or e in ("te", "teS"):
+            v = v / 10  # mm to cm
+        out.append(v / diameter if spec["by_diameter"] else v)
+    return out
+
+
+def localization_scores(per_image, thresholds, obj_ids, n_top):
+    """`pose_matching.match_poses` per image and `score.calc_localization_scores`: greedy matching in order of decreasing score -- an
+    estimate takes the free valid ground truth for which EVERY error element is below the threshold and below the best so far -- then
+    recall = matched / targets over everything and per object (0 for an object without targets; with n_top > 0 an image holds at most
+    n_top targets of an object).  per_image: [(gts, [dict(score, errors={gid: [elements]})])] -> (recall, {obj_id: recall})."""
+    tp, tars = {o: 0 for o in obj_ids}, {o: 0 for o in obj_ids}
+    for gts, ests in per_image:
+        count = {}
+        for g in gts:
+            if g["valid"]:
+                count[g["obj_id"]] = count.get(g["obj_id"], 0) + 1
+        for o, c in count.items():
+            tars[o] = tars.get(o, 0) + (min(n_top, c) if n_top > 0 else c)
+        taken = []
+        for e in sorted(ests, key=lambda e: e["score"], reverse=True):
+            best, best_err = -1, list(thresholds)
+            for gid, err in e["errors"].items():
+                if gts[gid]["valid"] and gid not in taken and all(err[i] < best_err[i] for i in range(len(thresholds))):
+                    best, best_err = gid, err
+            if best >= 0:
+                taken.append(best)
+        for gid in taken:
+            tp[gts[gid]["obj_id"]] = tp.get(gts[gid]["obj_id"], 0) + 1
+    n_tars = sum(tars.values())
+    return (sum(tp.values()) / float(n_tars) if n_tars else 0.0), {o: (tp[o] / float(tars[o]) if tars[o] else 0.0) for o in tars}
+
+
+def _error_block(thresholds, tables, weights):
+    """One entry of out["errors"] from [(recall, {obj_id: recall})] per threshold.  `weights` {obj_id: instances} weighs the mean over the
+    objects (vsd / mssd / mspd: bop_eval_utils.py:197-200, 270-277); None is the plain mean."""
+    recalls = [t[0] for t in tables]
+    objs = sorted(tables[0][1]) if tables else []
+    obj_recalls = {o: [t[1][o] for t in tables] for o in objs}
+    per_obj = [float(np.mean(obj_recalls[o])) for o in objs]
+    if weights is None or not objs:
+        mean_obj = float(np.mean(per_obj)) if objs else 0.0
+    else:
+        w = np.asarray([weights.get(o, 0) for o in objs], np.float64)
+        mean_obj = float((w / w.sum() * np.asarray(per_obj)).sum()) if w.sum() > 0 else 0.0
+    return dict(thresholds=thresholds, recalls=recalls, mean_recall=float(np.mean(recalls)), obj_recalls=obj_recalls, mean_obj_recall=mean_obj)
+
+
+def format_error_table(errors):
+    """The per-object table the reference prints after scoring (bop_eval_utils.summary_scores): objects in rows, `type_threshold` in
+    columns -- an area-under-curve type (AUC*, vsd, mssd, mspd) as ONE column `type_min:max` with the mean over its thresholds -- recalls
+    in percent, and an `Avg(n)` row with the mean over the objects (weighted by the instance counts for vsd / mssd / mspd)."""
+    def th_str(th):
+        return "-".join(dict.fromkeys("%g" % v for v in th))
+
+    cols, objs = [], []
+    for T, blk in errors.items():
+        objs = sorted(set(objs) | set(blk["obj_recalls"]))
+        rec = {o: np.asarray(v, np.float64).reshape(-1) for o, v in blk["obj_recalls"].items()}
+        if T in DEFAULT_ERROR_TYPES or ERROR_TYPES[T]["auc"]:
+            lo, hi = (0.05, 0.5) if T in ("vsd", "mssd") else (5, 50) if T == "mspd" else (blk["thresholds"][0][0], blk["thresholds"][-1][0])
+            cols.append((f"{T}_{lo:g}:{hi:g}", {o: float(v.mean()) for o, v in rec.items()}, blk["mean_obj_recall"]))
+        else:
+            for i, th in enumerate(blk["thresholds"]):
+                cols.append((f"{T}_{th_str(th)}", {o: float(v[i]) for o, v in rec.items()}, float(np.mean([v[i] for v in rec.values()])) if rec else 0.0))
+    rows = [["objects"] + [c[0] for c in cols]]
+    rows += [[str(o)] + ["%.2f" % (100.0 * c[1][o]) if o in c[1] else "-" for c in cols] for o in objs]
+    rows.append(["Avg(%d)" % len(objs)] + ["%.2f" % (100.0 * c[2]) for c in cols])
+    width = [max(len(r[i]) for r in rows) for i in range(len(rows[0]))]
+    return "\n".join("  ".join(v.ljust(width[i]) if i == 0 else v.rjust(width[i]) for i, v in enumerate(r)) for r in rows)
 
 
 def depth_to_dist(depth, K):
@@ -323,8 +647,62 @@ def _device_errors(walk, models, im_width, renderer, depth_images, vsd_delta, de
     return out
 
 
+def further_errors(walk, models, types, symmetric_obj_ids, n_top, device, targets, legacy):
+    """The `out["errors"]` blocks of `average_recall` for `types`.  `legacy` {"mssd" / "mspd": per-image sets, "vsd": one per tau or None}:
+    the BOP'19 errors already computed, tabulated per object too when `types` names them."""
+    symmetric = set(symmetric_obj_ids)
+    obj_ids = sorted(models)
+    pairs = metric_pairs(walk, models, types, symmetric)
+    values = host_pose_metrics(pairs, models) if device is None else device_pose_metrics(pairs, models, device)
+    apart = {p["key"]: p["apart"] for p in pairs}
+    if targets is not None:
+        weights = {}
+        for objs in targets.values():
+            for o, c in objs.items():
+                weights[o] = weights.get(o, 0) + c
+    else:
+        weights = {}
+        for _, _, gts, _, _ in walk:
+            for g in gts:
+                weights[g["obj_id"]] = weights.get(g["obj_id"], 0) + bool(g["valid"])
+
+    def listed(per_image):
+        return [(gts, [dict(score=e["score"], errors={gid: [v] for gid, v in e["errors"].items()}) for e in ests]) for gts, ests in per_image]
+
+    out = {}
+    for T in types:
+        if T == "vsd":
+            if legacy["vsd"] is None:
+                continue
+            tabs = [[localization_scores(listed(per_tau), [th], obj_ids, n_top) for th in VSD_THRESHOLDS] for per_tau in legacy["vsd"]]
+            flat = _error_block(None, [t for row in tabs for t in row], weights)
+            nt = len(VSD_THRESHOLDS)
+            out[T] = dict(flat, thresholds=dict(taus=[float(t) for t in VSD_TAUS], correct_th=[[float(t)] for t in VSD_THRESHOLDS]),
+                          recalls=[[t[0] for t in row] for row in tabs],
+                          obj_recalls={o: [v[i * nt:(i + 1) * nt] for i in range(len(tabs))] for o, v in flat["obj_recalls"].items()})
+        elif T in ("mssd", "mspd"):
+            ths = MSSD_THRESHOLDS if T == "mssd" else MSPD_THRESHOLDS
+            out[T] = _error_block([[float(t)] for t in ths], [localization_scores(listed(legacy[T]), [th], obj_ids, n_top) for th in ths], weights)
+        else:
+            per_image = []
+            for sid, iid, gts, K, picked in walk:
+                ests = []
+                for obj_id, rows in picked:
+                    for rank, r in enumerate(rows):
+                        errs = {}
+                        for gid, g in enumerate(gts):
+                            key = (sid, iid, obj_id, rank, gid)
+                            if g["obj_id"] == obj_id:
+                                errs[gid] = pair_error(T, values[key], models[obj_id]["diameter"], obj_id in symmetric, apart[key])
+                        ests.append(dict(score=r["score"], errors=errs))
+                per_image.append((gts, ests))
+            ths = ERROR_TYPES[T]["thresholds"]
+            out[T] = _error_block([list(th) for th in ths], [localization_scores(per_image, th, obj_ids, n_top) for th in ths], None)
+    return out
+
+
 def average_recall(results, scene_gt, models, cameras, im_width, n_top=1, renderer=None, depth_images=None, vsd_delta=VSD_DELTA, device=None,
-                   targets=None, chunk_bytes=DEVICE_CHUNK_BYTES):
+                   targets=None, chunk_bytes=DEVICE_CHUNK_BYTES, error_types=DEFAULT_ERROR_TYPES, symmetric_obj_ids=None):
     """results: `read_results` rows; scene_gt[scene_id][im_id] = list of {"obj_id", "R" (3,3), "t" (3,) mm, optional "valid"};
     models[obj_id] = {"pts" (n,3) mm, "diameter", "symmetries": [{"R","t"}] incl. identity}; cameras[scene_id][im_id] = K.
     Only the `n_top` best-scored estimates per (image, object) take part (BOP: the instance count of the target; `targets`: see `_walk`).
@@ -333,8 +711,21 @@ def average_recall(results, scene_gt, models, cameras, im_width, n_top=1, render
     Without `device` the errors come from `_host_errors` (numpy); a CUDA `device` selects `_device_errors`: same walk, same matching, the errors from csrc/bopscore.hip; VSD
     then needs a `render.HipDepthRenderer` of the image size on that device, and at most `chunk_bytes` of rendered maps exist at a time.
     The device route reads the test depth as float32, which is what `load_dataset` and the toolkit's `load_depth` return.
-    -> {"AR_VSD", "AR_MSSD", "AR_MSPD", "AR", "AR_MSSD_MSPD", "recalls_vsd" [tau][threshold], "recalls_mssd", "recalls_mspd"}."""
-    do_vsd = renderer is not None and depth_images is not None
+    -> {"AR_VSD", "AR_MSSD", "AR_MSPD", "AR", "AR_MSSD_MSPD", "recalls_vsd" [tau][threshold], "recalls_mssd", "recalls_mspd"}.
+    `error_types` (`parse_error_types`: names of KNOWN_ERROR_TYPES, a list or a comma-separated string): with the default the result is the
+    dictionary above.  Otherwise nothing is rendered unless "vsd" is named (AR_VSD = AR = None), and every named type T adds the block
+    below.  MSSD and MSPD are computed whatever `error_types` names, on purpose: they need no renderer, cost one launch per object beside
+    the further errors' (tens of microseconds per call), and with them "AR_MSSD", "AR_MSPD", "recalls_mssd" and "recalls_mspd" mean the
+    same in every scores file and on `--eval`'s AR line; VSD is the expensive one, and the only one left out.  The block:
+    out["errors"][T] = {"thresholds", "recalls" (per threshold, what `score.calc_localization_scores` calls "recall"), "mean_recall" (the
+    script's "average recall"), "obj_recalls" {obj_id: [per threshold]}, "mean_obj_recall" (mean over the objects of their mean recall;
+    for vsd / mssd / mspd weighted by the targets' instance counts)}; for "vsd" the lists are [tau][threshold].  The host route computes
+    them with this module's functions, the device route with `ops.pose_metrics` / `ops.adi`.  `symmetric_obj_ids`: the objects that take
+    ADI under ad / ABSad / AUCad (default `default_symmetric_obj_ids(models)`); the ids used are returned as out["symmetric_obj_ids"]."""
+    types = parse_error_types(error_types)
+    do_vsd = renderer is not None and depth_images is not None and "vsd" in types
+    if device is not None:
+        _cuda_device(device)
     walk = list(_walk(results, scene_gt, cameras, n_top, targets))
     if device is None:
         errors = _host_errors(walk, models, im_width, renderer if do_vsd else None, depth_images, vsd_delta)
@@ -356,7 +747,12 @@ def average_recall(results, scene_gt, models, cameras, im_width, n_top=1, render
             sets[k].append((gts, ests[k]))
         for ti in range(len(VSD_TAUS)):
             vsd_sets[ti].append((gts, vests[ti]))
-    return _recall_tables(sets, vsd_sets, do_vsd)
+    out = _recall_tables(sets, vsd_sets, do_vsd)
+    if types != DEFAULT_ERROR_TYPES:
+        sym_ids = default_symmetric_obj_ids(models) if symmetric_obj_ids is None else sorted(int(o) for o in symmetric_obj_ids)
+        out["errors"] = further_errors(walk, models, types, sym_ids, n_top, device, targets, dict(sets, vsd=vsd_sets if do_vsd else None))
+        out["symmetric_obj_ids"] = sym_ids
+    return out
 
 
 # ---- reading a BOP dataset folder for scoring ----------------------------------------------------------------------------------
@@ -534,25 +930,31 @@ def load_dataset(root, name, split, targets_filename="test_targets_bop19.json"):
 
 
 def score_csv(csv_path, root, name, split, device="cuda", device_scoring=True, n_top=-1, vsd_delta=None,
-              targets_filename="test_targets_bop19.json", renderer=None, chunk_bytes=DEVICE_CHUNK_BYTES):
+              targets_filename="test_targets_bop19.json", renderer=None, chunk_bytes=DEVICE_CHUNK_BYTES, error_types=None, symmetric_obj_ids=None):
     """Score the result file `csv_path` against the BOP dataset `<root>/<name>` and write `scores_bop19.json` beside it: the AR values
     and recall tables of `average_recall`, the number of scored targets ((image, object) entries of the targets file) and estimates,
     and the settings.  `device`: the GPU that renders (`render.HipDepthRenderer`, unless a `renderer` is handed in) and, with
     `device_scoring`, computes the errors; device_scoring=False is the host scorer on the same renders.  n_top as in `_walk` (-1: the
-    targets' instance counts); vsd_delta defaults to the dataset's (15 mm, ITODD 5 mm).  -> the dictionary written."""
+    targets' instance counts); vsd_delta defaults to the dataset's (15 mm, ITODD 5 mm).  `error_types` / `symmetric_obj_ids` as in
+    `average_recall` (None: the BOP'19 three): the file then also holds "errors", "error_types" and "symmetric_obj_ids", and no renderer
+    is built unless "vsd" is among the types.  -> the dictionary written."""
+    types = parse_error_types(error_types)
     data = load_dataset(root, name, split, targets_filename)
     results = read_results(csv_path)
     vsd_delta = VSD_DELTAS.get(name, VSD_DELTA) if vsd_delta is None else vsd_delta
     W, H = data["im_size"]
-    if renderer is None:
+    if renderer is None and "vsd" in types:
         from .render import HipDepthRenderer
 
         renderer = HipDepthRenderer(W, H, device=_cuda_device(device))
-    for obj_id, m in data["models"].items():
-        renderer.add_object(obj_id, m["verts"], m["faces"])
+    if renderer is not None:
+        for obj_id, m in data["models"].items():
+            renderer.add_object(obj_id, m["verts"], m["faces"])
     out = average_recall(results, data["scene_gt"], data["models"], data["cameras"], W, n_top=n_top, renderer=renderer,
                          depth_images=data["depth_images"], vsd_delta=vsd_delta, device=device if device_scoring else None,
-                         targets=data["targets"], chunk_bytes=chunk_bytes)
+                         targets=data["targets"], chunk_bytes=chunk_bytes, error_types=types, symmetric_obj_ids=symmetric_obj_ids)
+    if "errors" in out:
+        out["error_types"] = list(types)
     scored = sum(len(rows) for *_, picked in _walk(results, data["scene_gt"], data["cameras"], n_top, data["targets"]) for _, rows in picked)
     out.update(n_targets=sum(len(objs) for objs in data["targets"].values()), n_estimates=len(results), n_scored_estimates=scored, dataset=name,
                split=split, n_top=n_top, vsd_delta=float(vsd_delta), scorer="device" if device_scoring else "host")

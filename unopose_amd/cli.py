@@ -21,7 +21,15 @@
   comparison), writes ``scores_bop19.json`` beside the CSV and prints one line with AR_VSD / AR_MSSD / AR_MSPD / AR.  It reads
   ``<data_dir>/<dataset>``: ``bop_eval.targets_filename`` (default ``test_targets_bop19.json``), ``models_eval/``, the ``bop_eval.split``
   folder; ``bop_eval.n_top`` (default -1: the targets' instance counts) and ``bop_eval.vsd_delta`` (default 15 mm, ITODD 5 mm,
-  bop_eval_utils.py:348-362) are spelled as in the reference's ``val_cfg``.
+  bop_eval_utils.py:348-362) are spelled as in the reference's ``val_cfg``.  So is ``bop_eval.error_types``, a comma-separated string (or a
+  list) of the error types of ``lib/pysixd/scripts/eval_pose_results_more.py``: ``vsd, mssd, mspd, add, adi, ad, ABSadd, ABSadi, ABSad, AUCadd,
+  AUCadi, AUCad, re, te, rete, proj, reS, teS, reteS, projS`` (``bop_eval.error_types=ad,rete,proj`` is the reference's default table and needs
+  no renderer).  Each type beyond the BOP'19 three is scored on the same route -- ``ops.pose_metrics`` / ``ops.adi`` on the GPU, numpy with
+  ``--eval-device-off`` --, gets a line with its recalls after the AR line, and one per-object table follows (objects in rows,
+  ``type_threshold`` in columns, an ``Avg`` row, as ``bop_eval_utils.summary_scores`` lays it out); the scores file gains an ``errors`` key.
+  ``bop_eval.symmetric_obj_ids`` lists the objects that take ADI under ``ad / ABSad / AUCad`` (default: the objects whose ``models_info.json``
+  entry lists a symmetry -- not the reference's per-dataset id tables).  An unknown type is an error before any GPU work.  The mask-overlap
+  error ``cus`` stays out.
 * extras beyond the reference's line: ``--pipeline`` (two forwards in flight), ``--ref-cache`` (reference views encoded once),
   ``--device-prep`` (the provider builds each image's query crops, clouds and pixel indices on the rank's GPU: same items, same rows),
   ``--print-plan`` (resolve config and paths, touch no GPU: used by the CPU tests)."""
@@ -88,7 +96,7 @@ def result_paths(cfg, iteration=None):
 def eval_settings(cfg):
     """What ``--eval`` hands to ``bop_eval.score_csv``: the dataset folder of the provider and the ``bop_eval`` keys of the reference's
     ``val_cfg`` (bop_eval_utils.py:340-366)."""
-    from .bop_eval import VSD_DELTA, VSD_DELTAS
+    from .bop_eval import VSD_DELTA, VSD_DELTAS, parse_error_types
 
     dcfg = cfg["dataloader"]["test"]["dataset"]
     name = dcfg["eval_dataset_name"]
@@ -96,8 +104,13 @@ def eval_settings(cfg):
     if data_dir is None:
         raise ValueError("--eval: dataloader.test.dataset has no data_dir")
     be = cfg.get("bop_eval", {})
+    sym_ids = be.get("symmetric_obj_ids")
+    if isinstance(sym_ids, (str, int)):
+        sym_ids = [v for v in str(sym_ids).split(",") if v.strip()]
     return dict(root=data_dir, name=name, split=be.get("split", "test"), targets_filename=be.get("targets_filename", "test_targets_bop19.json"),
-                n_top=int(be.get("n_top", -1)), vsd_delta=float(be.get("vsd_delta", VSD_DELTAS.get(name, VSD_DELTA))))
+                n_top=int(be.get("n_top", -1)), vsd_delta=float(be.get("vsd_delta", VSD_DELTAS.get(name, VSD_DELTA))),
+                error_types=parse_error_types(be["error_types"]) if be.get("error_types") is not None else None,
+                symmetric_obj_ids=None if sym_ids is None else sorted(int(v) for v in sym_ids))
 
 
 def _launch_ranks(n, argv, poll_s=0.2):
@@ -163,6 +176,10 @@ def main(argv=None):
     cfg = apply_overrides(load_config(args.config_file), args.opts)
     out_dir, save_path = result_paths(cfg)
     c = Cfg(cfg)
+    if args.eval and isinstance(cfg.get("bop_eval"), dict):  # an unknown error type stops the run here, before any GPU work
+        from .bop_eval import parse_error_types
+
+        parse_error_types(cfg["bop_eval"].get("error_types"))
     if args.print_plan:
         plan = dict(save_path=save_path, dataset=c.dataloader.test.dataset.eval_dataset_name, checkpoint=c.misc.load_from,
                     amp=bool(c.test.amp.enabled), instance_batch_size=c.test.instance_batch_size, num_gpus=args.num_gpus,
@@ -173,6 +190,10 @@ def main(argv=None):
             ev = eval_settings(cfg)
             plan.update(eval_device=not args.eval_device_off, eval_paths=dataset_paths(ev["root"], ev["name"], ev["split"], ev["targets_filename"]),
                         eval_scores=osp.join(out_dir, "scores_bop19.json"), eval_n_top=ev["n_top"], eval_vsd_delta=ev["vsd_delta"])
+            if ev["error_types"] is not None:
+                plan.update(eval_error_types=list(ev["error_types"]))
+            if ev["symmetric_obj_ids"] is not None:
+                plan.update(eval_symmetric_obj_ids=ev["symmetric_obj_ids"])
         print(json.dumps(plan))
         return 0
     if not osp.exists(c.misc.load_from):  # save_unopose.sh:15-18
@@ -234,13 +255,22 @@ def main(argv=None):
     if lines is not None:
         print(f"{len(lines)} estimates -> {save_path}")
     if args.eval and int(os.environ.get("RANK", "0")) == 0:  # the other ranks wait at the teardown below
-        from .bop_eval import score_csv
+        from .bop_eval import format_error_table, score_csv
 
         ev = eval_settings(cfg)
         sc = score_csv(save_path, ev["root"], ev["name"], ev["split"], device=dev, device_scoring=not args.eval_device_off, n_top=ev["n_top"],
-                       vsd_delta=ev["vsd_delta"], targets_filename=ev["targets_filename"])
-        print("BOP19 %s-%s: AR_VSD %.4f  AR_MSSD %.4f  AR_MSPD %.4f  AR %.4f  (%d targets, %d estimates scored on the %s)"
-              % (ev["name"], ev["split"], sc["AR_VSD"], sc["AR_MSSD"], sc["AR_MSPD"], sc["AR"], sc["n_targets"], sc["n_scored_estimates"], sc["scorer"]))
+                       vsd_delta=ev["vsd_delta"], targets_filename=ev["targets_filename"], error_types=ev["error_types"],
+                       symmetric_obj_ids=ev["symmetric_obj_ids"])
+        ar = lambda v: "   n/a" if v is None else "%.4f" % v  # noqa: E731  (AR_VSD and AR need "vsd" among the error types)
+        print("BOP19 %s-%s: AR_VSD %s  AR_MSSD %s  AR_MSPD %s  AR %s  (%d targets, %d estimates scored on the %s)"
+              % (ev["name"], ev["split"], ar(sc["AR_VSD"]), ar(sc["AR_MSSD"]), ar(sc["AR_MSPD"]), ar(sc["AR"]), sc["n_targets"], sc["n_scored_estimates"],
+                 sc["scorer"]))
+        for T, blk in sc.get("errors", {}).items():
+            if T != "vsd":
+                print("%s %s: recalls %s  average recall %.4f" % (T, " ".join("-".join("%g" % v for v in th) for th in blk["thresholds"]),
+                                                                  " ".join("%.4f" % v for v in blk["recalls"]), blk["mean_recall"]))
+        if "errors" in sc:
+            print(format_error_table(sc["errors"]))
     if world > 1:
         dist.destroy_process_group()
     return 0

@@ -1,6 +1,7 @@
 """Pose errors of the BOP'19 scorer on the device (csrc/bopscore.hip): the integer counts inside `bop_eval.vsd` and the
-`bop_eval.mssd` / `mspd` errors, for many (estimate, ground truth) pairs per launch.  `bop_eval`'s host functions are the
-specification: the counts equal numpy's, the two distances agree with the BLAS-backed host code to rounding.
+`bop_eval.mssd` / `mspd` errors, for many (estimate, ground truth) pairs per launch, and the further errors of csrc/posemetrics.hip:
+`pose_metrics` (add, proj, re, te and the symmetry-aware projS, reS, teS) and `adi`.  `bop_eval`'s host functions are the
+specification: the counts equal numpy's, the distances and means agree with the BLAS-backed host code to rounding.
 
 The kernels trust the map indices they are given: the wrappers check every index against the map stacks on the host BEFORE
 anything is launched.  Depth maps are CUDA tensors; the small per-pair tables are host arrays; there is no CPU path."""
@@ -102,3 +103,87 @@ def pose_errors(pts, symmetries, R_est, t_est, R_gt, t_gt, K, device):
              ptr(out[0]), ptr(out[1]), stream_ptr(dev))
     return out[0], out[1]
 
+
+METRIC_NAMES = ("add", "proj", "re", "te", "projS", "reS", "teS")  # the rows unopose_pose_metrics writes
+
+
+@functools.lru_cache(maxsize=None)
+def adi_sizes():
+    """(points per LDS tile, query points per workgroup) of the ADI kernel."""
+    return int(lib().unopose_adi_tile_points()), int(lib().unopose_adi_slab_points())
+
+
+def _pair_table(name, device, pts, R_est, t_est, R_gt, t_gt):
+    """The host-side checks `pose_metrics` and `adi` share -> (device, pts (n,3), est (P,12), gt (P,12), finite (P,) bool)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"{name}: CPU not supported")
+    pts = np.ascontiguousarray(np.asarray(pts, dtype=np.float64).reshape(-1, 3))
+    R_est, R_gt = np.asarray(R_est, np.float64).reshape(-1, 9), np.asarray(R_gt, np.float64).reshape(-1, 9)
+    t_est, t_gt = np.asarray(t_est, np.float64).reshape(-1, 3), np.asarray(t_gt, np.float64).reshape(-1, 3)
+    P = R_est.shape[0]
+    if P < 1 or pts.shape[0] < 1 or not (R_gt.shape[0] == t_est.shape[0] == t_gt.shape[0] == P):
+        raise ValueError(f"{name}: {P} / {t_est.shape[0]} estimates (R / t), {R_gt.shape[0]} / {t_gt.shape[0]} ground truths, {pts.shape[0]} points")
+    if pts.shape[0] > 1 << 24 or not np.isfinite(pts).all():
+        raise ValueError(f"{name}: {pts.shape[0]} points (at most 2^24, all finite)")
+    est, gt = np.concatenate([R_est, t_est], axis=1), np.concatenate([R_gt, t_gt], axis=1)
+    finite = np.isfinite(est).all(axis=1) & np.isfinite(gt).all(axis=1)
+    return dev, pts, est, gt, finite
+
+
+def _with_nan_rows(out, finite, dev):
+    """A pair with a non-finite pose gets NaN in every output, decided on the host (the kernel saw an identity pose in its place)."""
+    if not finite.all():
+        out[..., torch.from_numpy(~finite).to(dev)] = float("nan")
+    return out
+
+
+def pose_metrics(pts, symmetries, R_est, t_est, R_gt, t_gt, K, device, proj_sym=True):
+    """`bop_eval.add`, `proj`, `re`, `te`, `proj_sym`, `re_sym`, `te_sym` for P pairs of one object in one launch.  pts (n, 3) model points;
+    symmetries: list of {"R", "t"} with the identity; R_est, R_gt (P, 3, 3), t_est, t_gt (P, 3); K (P, 3, 3) or (3, 3) -- host arrays,
+    float64 on the device, one upload.  -> {"add", "proj", "re", "te", "projS", "reS", "teS"}: float64 CUDA tensors (P,) in model units,
+    pixels and degrees; NaN for a pair with a non-finite pose.  Calling it twice gives the same bits.
+    projS is the only output whose work is points x symmetries: proj_sym=False leaves that pass out and the dictionary then has no "projS"
+    (reS / teS over a continuous symmetry's 315 poses cost a few hundred small products per pair)."""
+    dev, pts, est, gt, finite = _pair_table("pose_metrics", device, pts, R_est, t_est, R_gt, t_gt)
+    P = est.shape[0]
+    if len(symmetries) < 1:
+        raise ValueError("pose_metrics: no symmetries (the identity is one)")
+    syms = np.stack([np.concatenate([np.asarray(s["R"], np.float64).reshape(9), np.asarray(s["t"], np.float64).reshape(3)]) for s in symmetries])
+    K = np.asarray(K, np.float64).reshape(-1, 9)
+    if K.shape[0] not in (1, P) or not np.isfinite(K).all() or not np.isfinite(syms).all():
+        raise ValueError(f"pose_metrics: {K.shape[0]} intrinsics for {P} pairs, or a non-finite entry in K or the symmetries")
+    K = np.broadcast_to(K, (P, 9))
+    identity = np.concatenate([np.eye(3).reshape(9), [0.0, 0.0, 1.0]])
+    est, gt = np.where(finite[:, None], est, identity), np.where(finite[:, None], gt, identity)
+    host = np.concatenate([pts.reshape(-1), syms.reshape(-1), est.reshape(-1), gt.reshape(-1), K.reshape(-1)])
+    buf = torch.from_numpy(host).to(dev)  # one upload
+    o = np.cumsum([0, pts.size, syms.size, 12 * P, 12 * P, 9 * P])
+    part = [buf[o[i]:o[i + 1]] for i in range(5)]
+    out = torch.empty(len(METRIC_NAMES), P, dtype=torch.float64, device=dev)
+    with on_device(dev):
+        call("unopose_pose_metrics", ptr(part[0]), pts.shape[0], ptr(part[1]), syms.shape[0], ptr(part[2]), ptr(part[3]), ptr(part[4]), P, int(bool(proj_sym)),
+             ptr(out), stream_ptr(dev))
+    out = _with_nan_rows(out, finite, dev)
+    return {k: out[i] for i, k in enumerate(METRIC_NAMES) if proj_sym or k != "projS"}
+
+
+def adi(pts, R_est, t_est, R_gt, t_gt, device):
+    """`bop_eval.adi` for P <= 65535 pairs of one object: the mean distance from each model point in the ground-truth pose to the nearest
+    model point in the estimated pose, by a tiled brute force (n^2 distances per pair).  Host arrays in, one upload.
+    -> float64 CUDA tensor (P,), NaN for a pair with a non-finite pose.  Calling it twice gives the same bits."""
+    dev, pts, est, gt, finite = _pair_table("adi", device, pts, R_est, t_est, R_gt, t_gt)
+    P, n = est.shape[0], pts.shape[0]
+    if P > 65535:
+        raise ValueError(f"adi: {P} pairs per call (1 .. 65535)")
+    identity = np.concatenate([np.eye(3).reshape(9), np.zeros(3)])
+    est, gt = np.where(finite[:, None], est, identity), np.where(finite[:, None], gt, identity)
+    buf = torch.from_numpy(np.concatenate([pts.reshape(-1), est.reshape(-1), gt.reshape(-1)])).to(dev)  # one upload
+    o = np.cumsum([0, pts.size, 12 * P, 12 * P])
+    part = [buf[o[i]:o[i + 1]] for i in range(3)]
+    slabs = -(-n // adi_sizes()[1])
+    work = torch.empty(P * slabs, dtype=torch.float64, device=dev)
+    out = torch.empty(P, dtype=torch.float64, device=dev)
+    with on_device(dev):
+        call("unopose_adi", ptr(part[0]), n, ptr(part[1]), ptr(part[2]), P, ptr(work), ptr(out), stream_ptr(dev))
+    return _with_nan_rows(out, finite, dev)
