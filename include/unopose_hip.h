@@ -681,6 +681,22 @@ int unopose_pose_metrics(const double *pts, int n, const double *syms, int S, co
 int unopose_adi(const double *pts, int n, const double *est, const double *gt, int P, double *workspace, double *adi,
                 unopose_stream_t stream);
 
+/* Ground-truth visibility for G ground truths per launch (csrc/gtinfo.hip; unopose_amd/gt_info.py's gt_counts_host is the specification,
+ * i.e. lib/pysixd/scripts/calc_gt_info.py:97-171 and bop_toolkit's calc_gt_masks.py:92-108).
+ * canvas (n_canvas,3H,3W) float32: the object rendered by unopose_render_depth on the toolkit's enlarged canvas, principal point (cx + W, cy + H);
+ * test (n_test,H,W) float32 depth in mm; index (G,2) int32 = the ground truth's canvas map and test image (range-checked by the caller -- the
+ * kernel trusts them); params (G,5) float64 = fx, fy, cx, cy of the IMAGE and delta, the visibility tolerance.
+ * out (G, unopose_gt_visibility_ints() = 11) int32 = px_count_all (canvas pixels with depth > 0), px_count_valid (pixels of the central H x W crop
+ * with dist_gt > 0 and dist_test > 0), px_count_visib (crop pixels with ((float)dist_gt - (float)dist_test <= delta || dist_test == 0) && dist_gt > 0),
+ * then min x, min y, max x, max y of the silhouette on the canvas in image coordinates (canvas minus (W, H): may be negative) and the same four
+ * of the visible mask; the minimum / maximum of an empty set is INT_MAX / INT_MIN.  Equal to numpy's integers, every cast and evaluation
+ * order kept.  mask, mask_visib: both NULL, or (G,H,W) uint8 that receive 255 where dist_gt > 0 / where the pixel is visible, else 0.
+ * The canvas is read with 16-byte loads when 9 H W is a multiple of 4 and its base lies on a 16-byte boundary, else 4 bytes at a time.
+ * G <= 65535, 9 H W <= 2^30. */
+int unopose_gt_visibility_ints(void);
+int unopose_gt_visibility(const float *canvas, int n_canvas, const float *test, int n_test, const int *index, const double *params, int G,
+                          int H, int W, int *out, void *mask, void *mask_visib, unopose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

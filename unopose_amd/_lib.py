@@ -134,6 +134,8 @@ SIGNATURES = {
     "unopose_adi_slab_points": [],
     "unopose_pose_metrics": [_P, _I, _P, _I, _P, _P, _P, _I, _I, _P, _P],
     "unopose_adi": [_P, _I, _P, _P, _I, _P, _P, _P],
+    "unopose_gt_visibility_ints": [],
+    "unopose_gt_visibility": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
 }
 
 

@@ -24,7 +24,11 @@ functions (`lib/pysixd/pose_error.py`), csrc/posemetrics.hip the device route (`
 block with per-object recalls under `out["errors"]`.  The mask-overlap error `cus` and the other mask / bounding-box errors stay out.
 A deliberate difference: which objects take ADI under `ad / ABSad / AUCad` is not read from per-dataset id tables
 (`lib/pysixd/dataset_params.py:96-130`) but from the models -- an object whose `models_info.json` entry lists a discrete or continuous
-symmetry -- unless `symmetric_obj_ids=` (config key `bop_eval.symmetric_obj_ids`) says otherwise; the ids used are written with the scores."""
+symmetry -- unless `symmetric_obj_ids=` (config key `bop_eval.symmetric_obj_ids`) says otherwise; the ids used are written with the scores.
+Which ground truths count: by default every ground truth of a targeted object.  With `gt_info=` (the entries of `scene_gt_info.json`, read by
+`load_dataset(..., gt_info=True)` or computed by `unopose_amd.gt_info`) it is the toolkit's rule (`scripts/eval_calc_scores.py:205-238`): the
+`inst_count` most visible ground truths of each target object, or with `visib_gt_min >= 0` those visible to at least that fraction;
+`score_csv(..., gt_visibility="file" | "compute")` and the config keys `bop_eval.gt_visibility`, `bop_eval.visib_gt_min` select it."""
 import json
 import os.path as osp
 
@@ -448,12 +452,35 @@ def _recall_at(per_image, threshold):
     return tp / targets if targets else 0.0
 
 
-def _walk(results, scene_gt, cameras, n_top, targets):
+def _valid_by_visibility(gts, wanted, info, visib_gt_min, where):
+    """The toolkit's rule for which ground truths of an image count (eval_calc_scores.py:205-238) -> [bool] per ground truth.  `info`: the
+    image's `scene_gt_info.json` entries; only those of target objects are read.  visib_gt_min >= 0: a target whose visib_fract reaches it.
+    visib_gt_min < 0: of each target object the inst_count MOST VISIBLE ground truths, equal fractions in ground-truth order (Python's stable
+    `sorted(..., reverse=True)`, as the toolkit sorts); this rule needs the targets' instance counts."""
+    if info is None or len(info) != len(gts):
+        raise ValueError(f"bop_eval: gt_info of image {where} holds {0 if info is None else len(info)} entries for {len(gts)} ground truths")
+    mine = [gid for gid, g in enumerate(gts) if wanted is None or g["obj_id"] in wanted]
+    if visib_gt_min >= 0:
+        ok = {gid for gid in mine if info[gid]["visib_fract"] >= visib_gt_min}
+    else:
+        if wanted is None:
+            raise ValueError("bop_eval: the k-most-visible rule (visib_gt_min < 0) takes k from the targets' inst_count: pass `targets`")
+        ok, to_add = set(), dict(wanted)
+        for gid in sorted(mine, key=lambda gid: info[gid]["visib_fract"], reverse=True):
+            if to_add[gts[gid]["obj_id"]] > 0:
+                ok.add(gid)
+                to_add[gts[gid]["obj_id"]] -= 1
+    return [gid in ok for gid in range(len(gts))]
+
+
+def _walk(results, scene_gt, cameras, n_top, targets, gt_info=None, visib_gt_min=-1):
     """The images, objects and `n_top` selection both routes score: yields (scene_id, im_id, ground truths with "valid" filled in, K,
     [(obj_id, its estimates, best score first)]).  `targets[(scene_id, im_id)] = {obj_id: inst_count}` (the BOP targets file) limits the
     scoring to these images and objects -- a ground truth of another object is not a target (valid = False) -- and bounds the selection:
     n_top > 0 takes min(n_top, inst_count), n_top = -1 takes inst_count (the toolkit's "given by the number of GT poses"), 0 takes all.
-    Without `targets` every image of `scene_gt` is scored and any n_top <= 0 takes all."""
+    Without `targets` every image of `scene_gt` is scored and any n_top <= 0 takes all.
+    `gt_info[scene_id][im_id]` (the entries of `scene_gt_info.json`, `gt_info.compute_gt_info`) switches "valid" to the toolkit's rule,
+    `_valid_by_visibility` with `visib_gt_min`; None keeps every ground truth of a targeted object valid."""
     by_im = {}
     for r in results:
         by_im.setdefault((r["scene_id"], r["im_id"]), []).append(r)
@@ -462,7 +489,11 @@ def _walk(results, scene_gt, cameras, n_top, targets):
             wanted = None if targets is None else targets.get((sid, iid))
             if targets is not None and wanted is None:
                 continue
-            gts = [dict(g, valid=g.get("valid", True) and (wanted is None or g["obj_id"] in wanted)) for g in gts]
+            if gt_info is None:
+                gts = [dict(g, valid=g.get("valid", True) and (wanted is None or g["obj_id"] in wanted)) for g in gts]
+            else:
+                ok = _valid_by_visibility(gts, wanted, gt_info.get(sid, {}).get(iid), visib_gt_min, f"{sid}/{iid}")
+                gts = [dict(g, valid=g.get("valid", True) and ok[gid]) for gid, g in enumerate(gts)]
             per_obj = {}
             for r in by_im.get((sid, iid), []):
                 if wanted is None or r["obj_id"] in wanted:
@@ -702,7 +733,8 @@ def further_errors(walk, models, types, symmetric_obj_ids, n_top, device, target
 
 
 def average_recall(results, scene_gt, models, cameras, im_width, n_top=1, renderer=None, depth_images=None, vsd_delta=VSD_DELTA, device=None,
-                   targets=None, chunk_bytes=DEVICE_CHUNK_BYTES, error_types=DEFAULT_ERROR_TYPES, symmetric_obj_ids=None):
+                   targets=None, chunk_bytes=DEVICE_CHUNK_BYTES, error_types=DEFAULT_ERROR_TYPES, symmetric_obj_ids=None, gt_info=None,
+                   visib_gt_min=-1):
     """results: `read_results` rows; scene_gt[scene_id][im_id] = list of {"obj_id", "R" (3,3), "t" (3,) mm, optional "valid"};
     models[obj_id] = {"pts" (n,3) mm, "diameter", "symmetries": [{"R","t"}] incl. identity}; cameras[scene_id][im_id] = K.
     Only the `n_top` best-scored estimates per (image, object) take part (BOP: the instance count of the target; `targets`: see `_walk`).
@@ -721,12 +753,14 @@ def average_recall(results, scene_gt, models, cameras, im_width, n_top=1, render
     script's "average recall"), "obj_recalls" {obj_id: [per threshold]}, "mean_obj_recall" (mean over the objects of their mean recall;
     for vsd / mssd / mspd weighted by the targets' instance counts)}; for "vsd" the lists are [tau][threshold].  The host route computes
     them with this module's functions, the device route with `ops.pose_metrics` / `ops.adi`.  `symmetric_obj_ids`: the objects that take
-    ADI under ad / ABSad / AUCad (default `default_symmetric_obj_ids(models)`); the ids used are returned as out["symmetric_obj_ids"]."""
+    ADI under ad / ABSad / AUCad (default `default_symmetric_obj_ids(models)`); the ids used are returned as out["symmetric_obj_ids"].
+    `gt_info` / `visib_gt_min`: which ground truths count follows the toolkit's visibility rule (`_walk`, `_valid_by_visibility`) instead of
+    "every ground truth of a targeted object"; the matching, the recalls and every block of out["errors"] see the same flags."""
     types = parse_error_types(error_types)
     do_vsd = renderer is not None and depth_images is not None and "vsd" in types
     if device is not None:
         _cuda_device(device)
-    walk = list(_walk(results, scene_gt, cameras, n_top, targets))
+    walk = list(_walk(results, scene_gt, cameras, n_top, targets, gt_info, visib_gt_min))
     if device is None:
         errors = _host_errors(walk, models, im_width, renderer if do_vsd else None, depth_images, vsd_delta)
     else:
@@ -894,11 +928,12 @@ def dataset_paths(root, name, split, targets_filename="test_targets_bop19.json")
                 models=osp.join(base, "models_eval"), split=osp.join(base, split))
 
 
-def load_dataset(root, name, split, targets_filename="test_targets_bop19.json"):
+def load_dataset(root, name, split, targets_filename="test_targets_bop19.json", gt_info=False):
     """What `average_recall` needs of the BOP dataset `<root>/<name>`, for the images and objects of the targets file:
     models[obj_id] = {"pts", "verts", "faces", "diameter", "symmetries"} from models_eval/obj_XXXXXX.ply + models_info.json;
     scene_gt / cameras / depth_scales[scene_id][im_id] from <split>/<scene>/scene_gt.json and scene_camera.json; depth_images: a lazy
-    `DepthImages`; targets[(scene_id, im_id)] = {obj_id: inst_count}; im_size = (W, H) of the first target's depth image."""
+    `DepthImages`; targets[(scene_id, im_id)] = {obj_id: inst_count}; im_size = (W, H) of the first target's depth image.
+    gt_info=True adds "gt_info"[scene_id][im_id] from <split>/<scene>/scene_gt_info.json; a scene without the file is an error."""
     from .provider import SceneFiles, load_json
 
     paths = dataset_paths(root, name, split, targets_filename)
@@ -925,21 +960,66 @@ def load_dataset(root, name, split, targets_filename="test_targets_bop19.json"):
     if targets:
         sid, iid = next(iter(targets))
         im_size = depth_images[sid][iid].shape[::-1]
-    return dict(models=models, scene_gt=scene_gt, cameras=cameras, depth_scales=depth_scales, depth_images=depth_images, targets=targets,
-                im_size=im_size)
+    out = dict(models=models, scene_gt=scene_gt, cameras=cameras, depth_scales=depth_scales, depth_images=depth_images, targets=targets,
+               im_size=im_size)
+    if gt_info:
+        from .gt_info import load_gt_info
+
+        out["gt_info"] = load_gt_info(root, name, split, sorted(scene_gt))
+    return out
+
+
+def _computed_gt_info(data, delta, dev, on_device, chunk_bytes):
+    """`score_csv(gt_visibility="compute")`: `gt_info.compute_gt_info` for the ground truths of the targeted objects in the scored images (the
+    others are never valid and `load_dataset` holds no model of theirs: their entries are None) -> gt_info[scene_id][im_id]."""
+    from .gt_info import compute_gt_info
+    from .render import HipDepthRenderer
+
+    W, H = data["im_size"]
+    canvas = HipDepthRenderer(3 * W, 3 * H, device=dev)
+    for obj_id, m in data["models"].items():
+        canvas.add_object(obj_id, m["verts"], m["faces"])
+    keep = {sid: {iid: [gid for gid, g in enumerate(gts) if g["obj_id"] in data["targets"][(sid, iid)]] for iid, gts in ims.items()}
+            for sid, ims in data["scene_gt"].items()}
+    part = {sid: {iid: [data["scene_gt"][sid][iid][gid] for gid in gids] for iid, gids in ims.items()} for sid, ims in keep.items()}
+    info = compute_gt_info(part, data["cameras"], data["depth_images"], canvas, delta, device=dev if on_device else None, chunk_bytes=chunk_bytes)
+    out = {}
+    for sid, ims in keep.items():
+        for iid, gids in ims.items():
+            row = [None] * len(data["scene_gt"][sid][iid])
+            for gid, entry in zip(gids, info[sid][iid]):
+                row[gid] = entry
+            out.setdefault(sid, {})[iid] = row
+    return out
 
 
 def score_csv(csv_path, root, name, split, device="cuda", device_scoring=True, n_top=-1, vsd_delta=None,
-              targets_filename="test_targets_bop19.json", renderer=None, chunk_bytes=DEVICE_CHUNK_BYTES, error_types=None, symmetric_obj_ids=None):
+              targets_filename="test_targets_bop19.json", renderer=None, chunk_bytes=DEVICE_CHUNK_BYTES, error_types=None, symmetric_obj_ids=None,
+              gt_visibility="off", visib_gt_min=-1, gt_delta=None):
     """Score the result file `csv_path` against the BOP dataset `<root>/<name>` and write `scores_bop19.json` beside it: the AR values
     and recall tables of `average_recall`, the number of scored targets ((image, object) entries of the targets file) and estimates,
     and the settings.  `device`: the GPU that renders (`render.HipDepthRenderer`, unless a `renderer` is handed in) and, with
     `device_scoring`, computes the errors; device_scoring=False is the host scorer on the same renders.  n_top as in `_walk` (-1: the
     targets' instance counts); vsd_delta defaults to the dataset's (15 mm, ITODD 5 mm).  `error_types` / `symmetric_obj_ids` as in
     `average_recall` (None: the BOP'19 three): the file then also holds "errors", "error_types" and "symmetric_obj_ids", and no renderer
-    is built unless "vsd" is among the types.  -> the dictionary written."""
+    is built unless "vsd" is among the types.
+    `gt_visibility`: "off" -- every ground truth of a targeted object counts; "file" -- the toolkit's rule (`_valid_by_visibility` with
+    `visib_gt_min`) on the dataset's `scene_gt_info.json`, an error where the file is missing; "compute" -- the same rule on
+    `gt_info.compute_gt_info` for the targeted objects' ground truths in the scored images on the scoring device (on the host from HIP
+    renders with device_scoring=False), with the visibility tolerance `gt_delta` in mm: by default the dataset's (15, ITODD 5), which is what
+    `write_gt_info` and BOP's own files use -- NOT `vsd_delta`, which belongs to the VSD error; pass the `delta` a dataset's files were written
+    with to compute what they hold.  `visib_gt_min` under "off" and `gt_delta` without "compute" are errors.  The file then holds
+    "gt_visibility" and "visib_gt_min", under "compute" also "gt_delta".
+    -> the dictionary written."""
     types = parse_error_types(error_types)
-    data = load_dataset(root, name, split, targets_filename)
+    if gt_visibility not in ("off", "file", "compute"):
+        raise ValueError(f"bop_eval: gt_visibility {gt_visibility!r} (off, file or compute)")
+    if gt_visibility == "off" and visib_gt_min != -1:
+        raise ValueError("bop_eval: visib_gt_min has no effect with gt_visibility=\"off\" (file or compute)")
+    if gt_delta is not None and gt_visibility != "compute":
+        raise ValueError("bop_eval: gt_delta is the visibility tolerance of gt_visibility=\"compute\"")
+    gt_delta = VSD_DELTAS.get(name, VSD_DELTA) if gt_delta is None else gt_delta
+    data = load_dataset(root, name, split, targets_filename, gt_info=gt_visibility == "file")
     results = read_results(csv_path)
     vsd_delta = VSD_DELTAS.get(name, VSD_DELTA) if vsd_delta is None else vsd_delta
     W, H = data["im_size"]
@@ -950,12 +1030,18 @@ def score_csv(csv_path, root, name, split, device="cuda", device_scoring=True, n
     if renderer is not None:
         for obj_id, m in data["models"].items():
             renderer.add_object(obj_id, m["verts"], m["faces"])
+    gt_info = data.get("gt_info")
+    if gt_visibility == "compute":
+        gt_info = _computed_gt_info(data, gt_delta, _cuda_device(device), device_scoring, chunk_bytes)
     out = average_recall(results, data["scene_gt"], data["models"], data["cameras"], W, n_top=n_top, renderer=renderer,
                          depth_images=data["depth_images"], vsd_delta=vsd_delta, device=device if device_scoring else None,
-                         targets=data["targets"], chunk_bytes=chunk_bytes, error_types=types, symmetric_obj_ids=symmetric_obj_ids)
+                         targets=data["targets"], chunk_bytes=chunk_bytes, error_types=types, symmetric_obj_ids=symmetric_obj_ids,
+                         gt_info=gt_info, visib_gt_min=visib_gt_min)
+    if gt_visibility != "off":
+        out.update(gt_visibility=gt_visibility, visib_gt_min=visib_gt_min, **(dict(gt_delta=float(gt_delta)) if gt_visibility == "compute" else {}))
     if "errors" in out:
         out["error_types"] = list(types)
-    scored = sum(len(rows) for *_, picked in _walk(results, data["scene_gt"], data["cameras"], n_top, data["targets"]) for _, rows in picked)
+    scored = sum(len(rows) for *_, picked in _walk(results, data["scene_gt"], data["cameras"], n_top, data["targets"]) for _, rows in picked)  # not a matter of validity
     out.update(n_targets=sum(len(objs) for objs in data["targets"].values()), n_estimates=len(results), n_scored_estimates=scored, dataset=name,
                split=split, n_top=n_top, vsd_delta=float(vsd_delta), scorer="device" if device_scoring else "host")
     with open(osp.join(osp.dirname(osp.abspath(csv_path)), "scores_bop19.json"), "w") as f:

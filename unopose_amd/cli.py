@@ -29,7 +29,11 @@
   ``type_threshold`` in columns, an ``Avg`` row, as ``bop_eval_utils.summary_scores`` lays it out); the scores file gains an ``errors`` key.
   ``bop_eval.symmetric_obj_ids`` lists the objects that take ADI under ``ad / ABSad / AUCad`` (default: the objects whose ``models_info.json``
   entry lists a symmetry -- not the reference's per-dataset id tables).  An unknown type is an error before any GPU work.  The mask-overlap
-  error ``cus`` stays out.
+  error ``cus`` stays out.  ``bop_eval.gt_visibility`` (``off`` -- the default: every ground truth of a targeted object counts --, ``file`` or
+  ``compute``) selects the toolkit's rule for which ground truths count, from ``scene_gt_info.json`` or computed on the GPU
+  (``unopose_amd.gt_info``), with ``bop_eval.visib_gt_min`` as in the reference's ``eval_calc_scores.py`` (-1: the ``inst_count`` most visible) and, for ``compute``,
+  ``bop_eval.gt_delta``, the visibility tolerance in mm (default: the one BOP's files are made with, 15, ITODD 5); either key without the mode it
+  belongs to is an error.
 * extras beyond the reference's line: ``--pipeline`` (two forwards in flight), ``--ref-cache`` (reference views encoded once),
   ``--device-prep`` (the provider builds each image's query crops, clouds and pixel indices on the rank's GPU: same items, same rows),
   ``--print-plan`` (resolve config and paths, touch no GPU: used by the CPU tests)."""
@@ -110,7 +114,20 @@ def eval_settings(cfg):
     return dict(root=data_dir, name=name, split=be.get("split", "test"), targets_filename=be.get("targets_filename", "test_targets_bop19.json"),
                 n_top=int(be.get("n_top", -1)), vsd_delta=float(be.get("vsd_delta", VSD_DELTAS.get(name, VSD_DELTA))),
                 error_types=parse_error_types(be["error_types"]) if be.get("error_types") is not None else None,
-                symmetric_obj_ids=None if sym_ids is None else sorted(int(v) for v in sym_ids))
+                symmetric_obj_ids=None if sym_ids is None else sorted(int(v) for v in sym_ids),
+                **_gt_visibility(be))
+
+
+def _gt_visibility(be):
+    """`bop_eval.gt_visibility`, `bop_eval.visib_gt_min` and `bop_eval.gt_delta`; the last two mean nothing without the first and are an error then."""
+    mode, least, delta = be.get("gt_visibility"), be.get("visib_gt_min"), be.get("gt_delta")
+    if mode is not None and mode not in ("off", "file", "compute"):
+        raise ValueError(f"bop_eval.gt_visibility={mode!r} (off, file or compute)")
+    if least is not None and mode in (None, "off"):
+        raise ValueError("bop_eval.visib_gt_min needs bop_eval.gt_visibility=file or compute: without it every ground truth of a targeted object counts")
+    if delta is not None and mode != "compute":
+        raise ValueError("bop_eval.gt_delta is the visibility tolerance of bop_eval.gt_visibility=compute")
+    return dict(gt_visibility=mode, visib_gt_min=None if least is None else float(least), gt_delta=None if delta is None else float(delta))
 
 
 def _launch_ranks(n, argv, poll_s=0.2):
@@ -194,6 +211,12 @@ def main(argv=None):
                 plan.update(eval_error_types=list(ev["error_types"]))
             if ev["symmetric_obj_ids"] is not None:
                 plan.update(eval_symmetric_obj_ids=ev["symmetric_obj_ids"])
+            if ev["gt_visibility"] is not None:
+                plan.update(eval_gt_visibility=ev["gt_visibility"])
+            if ev["visib_gt_min"] is not None:
+                plan.update(eval_visib_gt_min=ev["visib_gt_min"])
+            if ev["gt_delta"] is not None:
+                plan.update(eval_gt_delta=ev["gt_delta"])
         print(json.dumps(plan))
         return 0
     if not osp.exists(c.misc.load_from):  # save_unopose.sh:15-18
@@ -260,7 +283,8 @@ def main(argv=None):
         ev = eval_settings(cfg)
         sc = score_csv(save_path, ev["root"], ev["name"], ev["split"], device=dev, device_scoring=not args.eval_device_off, n_top=ev["n_top"],
                        vsd_delta=ev["vsd_delta"], targets_filename=ev["targets_filename"], error_types=ev["error_types"],
-                       symmetric_obj_ids=ev["symmetric_obj_ids"])
+                       symmetric_obj_ids=ev["symmetric_obj_ids"], gt_visibility=ev["gt_visibility"] or "off",
+                       visib_gt_min=-1 if ev["visib_gt_min"] is None else ev["visib_gt_min"], gt_delta=ev["gt_delta"])
         ar = lambda v: "   n/a" if v is None else "%.4f" % v  # noqa: E731  (AR_VSD and AR need "vsd" among the error types)
         print("BOP19 %s-%s: AR_VSD %s  AR_MSSD %s  AR_MSPD %s  AR %s  (%d targets, %d estimates scored on the %s)"
               % (ev["name"], ev["split"], ar(sc["AR_VSD"]), ar(sc["AR_MSSD"]), ar(sc["AR_MSPD"]), ar(sc["AR"]), sc["n_targets"], sc["n_scored_estimates"],

@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "visib.h"
 
 namespace unopose {
 
@@ -34,11 +35,6 @@ constexpr int POSE_SYM_BLOCK = 4;
 struct VsdTaus {
   double v[VSD_MAX_TAUS];  // unused entries hold +inf: their counts stay 0
 };
-
-__device__ __forceinline__ double vsd_dist(double pre_x, double pre_y, float depth) {
-  const double d = (double)depth, a = pre_x * d, b = pre_y * d;
-  return sqrt(a * a + b * b + d * d);
-}
 
 // one pixel into the thread's counters
 __device__ __forceinline__ void vsd_pixel(int idx, int W, float d_test, float d_gt, float d_est, double fx, double fy, double cx, double cy,

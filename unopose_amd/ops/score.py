@@ -1,6 +1,7 @@
 """Pose errors of the BOP'19 scorer on the device (csrc/bopscore.hip): the integer counts inside `bop_eval.vsd` and the
 `bop_eval.mssd` / `mspd` errors, for many (estimate, ground truth) pairs per launch, and the further errors of csrc/posemetrics.hip:
-`pose_metrics` (add, proj, re, te and the symmetry-aware projS, reS, teS) and `adi`.  `bop_eval`'s host functions are the
+`pose_metrics` (add, proj, re, te and the symmetry-aware projS, reS, teS) and `adi`; `gt_visibility` (csrc/gtinfo.hip) is the
+ground-truth side, the integers behind `scene_gt_info.json` and the two masks.  `bop_eval`'s and `gt_info`'s host functions are the
 specification: the counts equal numpy's, the distances and means agree with the BLAS-backed host code to rounding.
 
 The kernels trust the map indices they are given: the wrappers check every index against the map stacks on the host BEFORE
@@ -31,10 +32,10 @@ def _maps(x, name, hw=None):
     return x
 
 
-def _index(idx, P, limit, name):
+def _index(idx, P, limit, name, op="vsd_counts"):
     idx = np.arange(P, dtype=np.int64) if idx is None else np.asarray(idx, dtype=np.int64).reshape(-1)
     if idx.shape[0] != P or idx.min() < 0 or idx.max() >= limit:
-        raise ValueError(f"vsd_counts: {name} must hold {P} indices inside [0, {limit})")
+        raise ValueError(f"{op}: {name} must hold {P} indices inside [0, {limit})")
     return idx
 
 
@@ -76,6 +77,46 @@ def vsd_counts(depth_test, depth_gt, depth_est, K4, delta, diameter, taus, image
         call("unopose_vsd_counts", ptr(depth_test), int(depth_test.shape[0]), ptr(depth_gt), int(depth_gt.shape[0]), ptr(depth_est),
              int(depth_est.shape[0]), ptr(index_d), ptr(pairs_d), ctypes.c_void_p(taus.ctypes.data), T, P, hw[0], hw[1], ptr(counts), stream_ptr(dev))
     return counts[:, :2 + T].to(torch.int64)
+
+
+GT_COLUMNS = ("px_count_all", "px_count_valid", "px_count_visib", "obj_xmin", "obj_ymin", "obj_xmax", "obj_ymax", "visib_xmin", "visib_ymin",
+              "visib_xmax", "visib_ymax")  # the row unopose_gt_visibility writes per ground truth
+
+
+def gt_visibility(depth_test, canvas, K4, delta, image_index=None, canvas_index=None, masks=False):
+    """The integers of `gt_info.gt_counts_host` for G ground truths over one image size (csrc/gtinfo.hip).  depth_test (n_test, H, W):
+    float32 CUDA depth in mm; canvas (n_canvas, 3H, 3W): the objects rendered on the toolkit's enlarged canvas with the principal point at
+    (cx + W, cy + H), straight from a `HipDepthRenderer(3W, 3H).render_batch`; ground truth g is canvas[canvas_index[g]] in front of
+    depth_test[image_index[g]] (each index defaults to g).  K4 (G, 4) or (4,) = fx, fy, cx, cy of the image; delta: scalar or (G,).
+    -> int64 CUDA tensor (G, 11), columns `GT_COLUMNS`: the three pixel counts, then min x, min y, max x, max y of the silhouette on the
+    canvas in image coordinates (negative where the object leaves the image) and of the visible mask; the minimum / maximum of an empty
+    set is the largest / smallest int32.  With masks=True also two uint8 CUDA tensors (G, H, W), 0 / 255: `dist_gt > 0` and the visible mask."""
+    _maps(depth_test, "gt_visibility: depth_test")
+    H, W = (int(v) for v in depth_test.shape[1:])
+    _maps(canvas, "gt_visibility: canvas", (3 * H, 3 * W))
+    dev = depth_test.device
+    if canvas.device != dev:
+        raise RuntimeError("gt_visibility: the maps live on different devices")
+    G = len(canvas_index) if canvas_index is not None else len(image_index) if image_index is not None else int(canvas.shape[0])
+    if not 1 <= G <= 65535:
+        raise ValueError(f"gt_visibility: {G} ground truths per call (1 .. 65535)")
+    if 9 * H * W > 1 << 30:
+        raise ValueError(f"gt_visibility: a canvas of {3 * H} x {3 * W} pixels (at most 2^30)")
+    idx = np.stack([_index(canvas_index, G, canvas.shape[0], "canvas_index", "gt_visibility"),
+                    _index(image_index, G, depth_test.shape[0], "image_index", "gt_visibility")], axis=1).astype(np.int32)
+    params = np.empty((G, 5), dtype=np.float64)
+    params[:, :4] = np.asarray(K4, dtype=np.float64).reshape(-1, 4)
+    params[:, 4] = [vsd_delta_as_compared(d) for d in delta] if np.ndim(delta) else vsd_delta_as_compared(delta)
+    idx_d, params_d = torch.from_numpy(idx).to(dev), torch.from_numpy(params).to(dev)
+    n = int(lib().unopose_gt_visibility_ints())
+    out = torch.empty(G, n, dtype=torch.int32, device=dev)
+    m = torch.empty(2, G, H, W, dtype=torch.uint8, device=dev) if masks else None
+    null = ctypes.c_void_p(None)
+    with on_device(dev):
+        call("unopose_gt_visibility", ptr(canvas), int(canvas.shape[0]), ptr(depth_test), int(depth_test.shape[0]), ptr(idx_d), ptr(params_d), G, H, W,
+             ptr(out), ptr(m[0]) if masks else null, ptr(m[1]) if masks else null, stream_ptr(dev))
+    out = out.to(torch.int64)
+    return (out, m[0], m[1]) if masks else out
 
 
 def pose_errors(pts, symmetries, R_est, t_est, R_gt, t_gt, K, device):

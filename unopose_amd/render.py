@@ -21,8 +21,9 @@ class HipDepthRenderer:
         assert v.dim() == 2 and v.shape[1] == 3 and f.dim() == 2 and f.shape[1] == 3 and int(f.max()) < v.shape[0]
         self.models[obj_id] = (v, f)
 
-    def render_batch(self, obj_id, Rs, ts, K4):
-        """Rs (P,3,3), ts (P,3), K4 (P,4) or (4,) = fx, fy, cx, cy -> depth (P,H,W) float32 tensor on the device."""
+    def render_batch(self, obj_id, Rs, ts, K4, out=None):
+        """Rs (P,3,3), ts (P,3), K4 (P,4) or (4,) = fx, fy, cx, cy -> depth (P,H,W) float32 tensor on the device: a new one, or `out`
+        (contiguous, of that shape, on the device) for a caller that renders several objects into one stack."""
         v, f = self.models[obj_id]
         Rs = torch.as_tensor(np.asarray(Rs, np.float32)).reshape(-1, 9)
         ts = torch.as_tensor(np.asarray(ts, np.float32)).reshape(-1, 3)
@@ -30,7 +31,12 @@ class HipDepthRenderer:
         Rt = torch.cat([Rs, ts], 1).contiguous().to(self.device)
         K4 = torch.as_tensor(np.asarray(K4, np.float32)).reshape(-1, 4)
         K4 = (K4.expand(P, 4) if K4.shape[0] == 1 else K4).contiguous().to(self.device)
-        depth = torch.empty(P, self.H, self.W, dtype=torch.float32, device=self.device)
+        if out is None:
+            depth = torch.empty(P, self.H, self.W, dtype=torch.float32, device=self.device)
+        else:
+            if out.dtype != torch.float32 or tuple(out.shape) != (P, self.H, self.W) or not out.is_contiguous() or out.device != Rt.device:
+                raise RuntimeError(f"render_batch: out must be a contiguous float32 tensor {(P, self.H, self.W)} on {Rt.device}, not {out.dtype} {tuple(out.shape)} on {out.device}")
+            depth = out
         with on_device(self.device):
             call("unopose_render_depth", ptr(v), v.shape[0], ptr(f), f.shape[0], ptr(Rt), ptr(K4), P, self.H, self.W, ptr(depth),
                  stream_ptr(self.device))
