@@ -697,6 +697,24 @@ int unopose_gt_visibility_ints(void);
 int unopose_gt_visibility(const float *canvas, int n_canvas, const float *test, int n_test, const int *index, const double *params, int G,
                           int H, int W, int *out, void *mask, void *mask_visib, unopose_stream_t stream);
 
+/* models_info.json for M objects per launch sequence (csrc/modelinfo.hip; unopose_amd/model_info.py's extent_host is the specification, i.e.
+ * bop_toolkit's scripts/calc_model_info.py:33-38 with misc.calc_pts_diameter, misc.py:272-286).  All float64.
+ * pts (N,3): the objects' points packed one after the other; object k owns rows offsets[k] .. offsets[k + 1] - 1.  The table of M + 1 row
+ * offsets is handed over twice: `offsets` in HOST memory, validated here before anything is launched (offsets[0] = 0, increasing, every object
+ * 1 .. 2^24 points, 1 <= M <= 65535), and `offsets_dev`, the same table in device memory, which the kernels read; they touch no row outside
+ * [0, offsets[M]) whatever it holds.
+ * out (M, unopose_pts_extent_doubles() = 7) = min x, y, z, max x, y, z and the largest (dx*dx + dy*dy) + dz*dz over all pairs of the object's
+ * points, the pair (i, i) included: bit-equal to the host's float64 value (no contraction, a maximum has no order); the square root is the
+ * caller's.  Every entry is written; what the buffers held before does not matter.
+ * prune != 0: only the points that can belong to a pair at least as far apart as a pair found by two farthest-point sweeps enter the
+ * all-pairs pass (triangle inequality about the mean, margin 2^-40); the result is the same bits.  kept (N,3) float64 and kept_count (M)
+ * int64 are device workspace for the survivors (both may be NULL with prune = 0).
+ * The all-pairs pass works in tiles of unopose_pts_extent_tile_points() points and visits the tile pairs (a, b >= a) of each object. */
+int unopose_pts_extent_tile_points(void);
+int unopose_pts_extent_doubles(void);
+int unopose_pts_extent(const double *pts, const long long *offsets, const long long *offsets_dev, int M, int prune, double *kept,
+                       long long *kept_count, double *out, unopose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,9 @@ SIGNATURES = {
     "unopose_adi": [_P, _I, _P, _P, _I, _P, _P, _P],
     "unopose_gt_visibility_ints": [],
     "unopose_gt_visibility": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "unopose_pts_extent_tile_points": [],
+    "unopose_pts_extent_doubles": [],
+    "unopose_pts_extent": [_P, _P, _P, _I, _I, _P, _P, _P, _P],
 }
 
 

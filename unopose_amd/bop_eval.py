@@ -28,7 +28,9 @@ symmetry -- unless `symmetric_obj_ids=` (config key `bop_eval.symmetric_obj_ids`
 Which ground truths count: by default every ground truth of a targeted object.  With `gt_info=` (the entries of `scene_gt_info.json`, read by
 `load_dataset(..., gt_info=True)` or computed by `unopose_amd.gt_info`) it is the toolkit's rule (`scripts/eval_calc_scores.py:205-238`): the
 `inst_count` most visible ground truths of each target object, or with `visib_gt_min >= 0` those visible to at least that fraction;
-`score_csv(..., gt_visibility="file" | "compute")` and the config keys `bop_eval.gt_visibility`, `bop_eval.visib_gt_min` select it."""
+`score_csv(..., gt_visibility="file" | "compute")` and the config keys `bop_eval.gt_visibility`, `bop_eval.visib_gt_min` select it.
+Where the diameters come from: `models_eval/models_info.json`, or with `models_info="compute"` (config key `bop_eval.models_info`) the models'
+own vertices (`unopose_amd.model_info`, csrc/modelinfo.hip), for meshes that come without the file."""
 import json
 import os.path as osp
 
@@ -928,24 +930,43 @@ def dataset_paths(root, name, split, targets_filename="test_targets_bop19.json")
                 models=osp.join(base, "models_eval"), split=osp.join(base, split))
 
 
-def load_dataset(root, name, split, targets_filename="test_targets_bop19.json", gt_info=False):
+MODELS_INFO_MODES = ("file", "compute")
+
+
+def _models_info_mode(mode):
+    if mode not in MODELS_INFO_MODES:
+        raise ValueError(f"bop_eval: models_info {mode!r} (file or compute)")
+    return mode
+
+
+def load_dataset(root, name, split, targets_filename="test_targets_bop19.json", gt_info=False, models_info="file", device=None):
     """What `average_recall` needs of the BOP dataset `<root>/<name>`, for the images and objects of the targets file:
     models[obj_id] = {"pts", "verts", "faces", "diameter", "symmetries"} from models_eval/obj_XXXXXX.ply + models_info.json;
     scene_gt / cameras / depth_scales[scene_id][im_id] from <split>/<scene>/scene_gt.json and scene_camera.json; depth_images: a lazy
     `DepthImages`; targets[(scene_id, im_id)] = {obj_id: inst_count}; im_size = (W, H) of the first target's depth image.
-    gt_info=True adds "gt_info"[scene_id][im_id] from <split>/<scene>/scene_gt_info.json; a scene without the file is an error."""
+    gt_info=True adds "gt_info"[scene_id][im_id] from <split>/<scene>/scene_gt_info.json; a scene without the file is an error.
+    models_info="compute": the diameters are not read but computed from the targeted objects' vertices (`model_info.compute_models_info`: on
+    the CUDA `device`, on the host without one -- equal bits), so a dataset without models_info.json can be scored; the symmetries still come
+    from the file where it exists (they are annotations), else every object has the identity only."""
     from .provider import SceneFiles, load_json
 
+    _models_info_mode(models_info)
     paths = dataset_paths(root, name, split, targets_filename)
     targets = {}
     for t in load_json(paths["targets"]):
         targets.setdefault((int(t["scene_id"]), int(t["im_id"])), {})[int(t["obj_id"])] = int(t.get("inst_count", 1))
-    info = load_json(paths["models_info"])
+    info = load_json(paths["models_info"]) if models_info == "file" or osp.exists(paths["models_info"]) else {}
+    meshes = {obj_id: read_ply(osp.join(paths["models"], f"obj_{obj_id:06d}.ply")) for obj_id in sorted({o for objs in targets.values() for o in objs})}
+    if models_info == "compute":
+        from .model_info import compute_models_info
+
+        diameters = {o: e["diameter"] for o, e in compute_models_info({o: m["pts"] for o, m in meshes.items()}, device=device).items()}
+    else:
+        diameters = {o: float(info[str(o)]["diameter"]) for o in meshes}
     models = {}
-    for obj_id in sorted({o for objs in targets.values() for o in objs}):
-        mesh = read_ply(osp.join(paths["models"], f"obj_{obj_id:06d}.ply"))
-        models[obj_id] = dict(pts=mesh["pts"], verts=mesh["pts"], faces=mesh["faces"], diameter=float(info[str(obj_id)]["diameter"]),
-                              symmetries=symmetry_transformations(info[str(obj_id)]))
+    for obj_id, mesh in meshes.items():
+        models[obj_id] = dict(pts=mesh["pts"], verts=mesh["pts"], faces=mesh["faces"], diameter=diameters[obj_id],
+                              symmetries=symmetry_transformations(info.get(str(obj_id), {})))
     files = SceneFiles()
     scene_gt, cameras, depth_scales = {}, {}, {}
     for sid, iid in targets:
@@ -995,7 +1016,7 @@ def _computed_gt_info(data, delta, dev, on_device, chunk_bytes):
 
 def score_csv(csv_path, root, name, split, device="cuda", device_scoring=True, n_top=-1, vsd_delta=None,
               targets_filename="test_targets_bop19.json", renderer=None, chunk_bytes=DEVICE_CHUNK_BYTES, error_types=None, symmetric_obj_ids=None,
-              gt_visibility="off", visib_gt_min=-1, gt_delta=None):
+              gt_visibility="off", visib_gt_min=-1, gt_delta=None, models_info=None):
     """Score the result file `csv_path` against the BOP dataset `<root>/<name>` and write `scores_bop19.json` beside it: the AR values
     and recall tables of `average_recall`, the number of scored targets ((image, object) entries of the targets file) and estimates,
     and the settings.  `device`: the GPU that renders (`render.HipDepthRenderer`, unless a `renderer` is handed in) and, with
@@ -1010,8 +1031,13 @@ def score_csv(csv_path, root, name, split, device="cuda", device_scoring=True, n
     `write_gt_info` and BOP's own files use -- NOT `vsd_delta`, which belongs to the VSD error; pass the `delta` a dataset's files were written
     with to compute what they hold.  `visib_gt_min` under "off" and `gt_delta` without "compute" are errors.  The file then holds
     "gt_visibility" and "visib_gt_min", under "compute" also "gt_delta".
+    `models_info`: None or "file" -- the diameters of models_eval/models_info.json; "compute" -- the diameters computed from the models_eval
+    vertices of the targeted objects (`load_dataset`), on the scoring device or, with device_scoring=False, on the host: a dataset without the
+    file can be scored.  The file holds "models_info" only when the option is given.
     -> the dictionary written."""
     types = parse_error_types(error_types)
+    if models_info is not None:
+        _models_info_mode(models_info)
     if gt_visibility not in ("off", "file", "compute"):
         raise ValueError(f"bop_eval: gt_visibility {gt_visibility!r} (off, file or compute)")
     if gt_visibility == "off" and visib_gt_min != -1:
@@ -1019,7 +1045,8 @@ def score_csv(csv_path, root, name, split, device="cuda", device_scoring=True, n
     if gt_delta is not None and gt_visibility != "compute":
         raise ValueError("bop_eval: gt_delta is the visibility tolerance of gt_visibility=\"compute\"")
     gt_delta = VSD_DELTAS.get(name, VSD_DELTA) if gt_delta is None else gt_delta
-    data = load_dataset(root, name, split, targets_filename, gt_info=gt_visibility == "file")
+    data = load_dataset(root, name, split, targets_filename, gt_info=gt_visibility == "file", models_info=models_info or "file",
+                        device=_cuda_device(device) if device_scoring and models_info == "compute" else None)
     results = read_results(csv_path)
     vsd_delta = VSD_DELTAS.get(name, VSD_DELTA) if vsd_delta is None else vsd_delta
     W, H = data["im_size"]
@@ -1039,6 +1066,8 @@ def score_csv(csv_path, root, name, split, device="cuda", device_scoring=True, n
                          gt_info=gt_info, visib_gt_min=visib_gt_min)
     if gt_visibility != "off":
         out.update(gt_visibility=gt_visibility, visib_gt_min=visib_gt_min, **(dict(gt_delta=float(gt_delta)) if gt_visibility == "compute" else {}))
+    if models_info is not None:
+        out.update(models_info=models_info)
     if "errors" in out:
         out["error_types"] = list(types)
     scored = sum(len(rows) for *_, picked in _walk(results, data["scene_gt"], data["cameras"], n_top, data["targets"]) for _, rows in picked)  # not a matter of validity

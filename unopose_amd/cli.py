@@ -33,7 +33,10 @@
   ``compute``) selects the toolkit's rule for which ground truths count, from ``scene_gt_info.json`` or computed on the GPU
   (``unopose_amd.gt_info``), with ``bop_eval.visib_gt_min`` as in the reference's ``eval_calc_scores.py`` (-1: the ``inst_count`` most visible) and, for ``compute``,
   ``bop_eval.gt_delta``, the visibility tolerance in mm (default: the one BOP's files are made with, 15, ITODD 5); either key without the mode it
-  belongs to is an error.
+  belongs to is an error.  ``bop_eval.models_info`` (``file`` -- the default: the diameters of ``models_eval/models_info.json`` --, or ``compute``)
+  takes the diameters from the ``models_eval`` vertices of the targeted objects instead (``unopose_amd.model_info``: on the GPU, on the host with
+  ``--eval-device-off``; the same bits), so meshes that come without the file can be scored; symmetries are still read from the file where it
+  exists.  Any other value is an error before any GPU work.
 * extras beyond the reference's line: ``--pipeline`` (two forwards in flight), ``--ref-cache`` (reference views encoded once),
   ``--device-prep`` (the provider builds each image's query crops, clouds and pixel indices on the rank's GPU: same items, same rows),
   ``--print-plan`` (resolve config and paths, touch no GPU: used by the CPU tests)."""
@@ -115,7 +118,15 @@ def eval_settings(cfg):
                 n_top=int(be.get("n_top", -1)), vsd_delta=float(be.get("vsd_delta", VSD_DELTAS.get(name, VSD_DELTA))),
                 error_types=parse_error_types(be["error_types"]) if be.get("error_types") is not None else None,
                 symmetric_obj_ids=None if sym_ids is None else sorted(int(v) for v in sym_ids),
-                **_gt_visibility(be))
+                **_gt_visibility(be), models_info=_models_info(be))
+
+
+def _models_info(be):
+    """`bop_eval.models_info`: file or compute; None when the key is not given."""
+    mode = be.get("models_info")
+    if mode is not None and mode not in ("file", "compute"):
+        raise ValueError(f"bop_eval.models_info={mode!r} (file or compute)")
+    return mode
 
 
 def _gt_visibility(be):
@@ -197,6 +208,7 @@ def main(argv=None):
         from .bop_eval import parse_error_types
 
         parse_error_types(cfg["bop_eval"].get("error_types"))
+        _models_info(cfg["bop_eval"])
     if args.print_plan:
         plan = dict(save_path=save_path, dataset=c.dataloader.test.dataset.eval_dataset_name, checkpoint=c.misc.load_from,
                     amp=bool(c.test.amp.enabled), instance_batch_size=c.test.instance_batch_size, num_gpus=args.num_gpus,
@@ -217,6 +229,8 @@ def main(argv=None):
                 plan.update(eval_visib_gt_min=ev["visib_gt_min"])
             if ev["gt_delta"] is not None:
                 plan.update(eval_gt_delta=ev["gt_delta"])
+            if ev["models_info"] is not None:
+                plan.update(eval_models_info=ev["models_info"])
         print(json.dumps(plan))
         return 0
     if not osp.exists(c.misc.load_from):  # save_unopose.sh:15-18
@@ -284,7 +298,7 @@ def main(argv=None):
         sc = score_csv(save_path, ev["root"], ev["name"], ev["split"], device=dev, device_scoring=not args.eval_device_off, n_top=ev["n_top"],
                        vsd_delta=ev["vsd_delta"], targets_filename=ev["targets_filename"], error_types=ev["error_types"],
                        symmetric_obj_ids=ev["symmetric_obj_ids"], gt_visibility=ev["gt_visibility"] or "off",
-                       visib_gt_min=-1 if ev["visib_gt_min"] is None else ev["visib_gt_min"], gt_delta=ev["gt_delta"])
+                       visib_gt_min=-1 if ev["visib_gt_min"] is None else ev["visib_gt_min"], gt_delta=ev["gt_delta"], models_info=ev["models_info"])
         ar = lambda v: "   n/a" if v is None else "%.4f" % v  # noqa: E731  (AR_VSD and AR need "vsd" among the error types)
         print("BOP19 %s-%s: AR_VSD %s  AR_MSSD %s  AR_MSPD %s  AR %s  (%d targets, %d estimates scored on the %s)"
               % (ev["name"], ev["split"], ar(sc["AR_VSD"]), ar(sc["AR_MSSD"]), ar(sc["AR_MSPD"]), ar(sc["AR"]), sc["n_targets"], sc["n_scored_estimates"],

@@ -1,7 +1,8 @@
 """Pose errors of the BOP'19 scorer on the device (csrc/bopscore.hip): the integer counts inside `bop_eval.vsd` and the
 `bop_eval.mssd` / `mspd` errors, for many (estimate, ground truth) pairs per launch, and the further errors of csrc/posemetrics.hip:
 `pose_metrics` (add, proj, re, te and the symmetry-aware projS, reS, teS) and `adi`; `gt_visibility` (csrc/gtinfo.hip) is the
-ground-truth side, the integers behind `scene_gt_info.json` and the two masks.  `bop_eval`'s and `gt_info`'s host functions are the
+ground-truth side, the integers behind `scene_gt_info.json` and the two masks; `pts_extent` (csrc/modelinfo.hip) the model side, the box
+and the diameter behind `models_info.json`.  `bop_eval`'s and `gt_info`'s host functions are the
 specification: the counts equal numpy's, the distances and means agree with the BLAS-backed host code to rounding.
 
 The kernels trust the map indices they are given: the wrappers check every index against the map stacks on the host BEFORE
@@ -228,3 +229,65 @@ def adi(pts, R_est, t_est, R_gt, t_gt, device):
     with on_device(dev):
         call("unopose_adi", ptr(part[0]), n, ptr(part[1]), ptr(part[2]), P, ptr(work), ptr(out), stream_ptr(dev))
     return _with_nan_rows(out, finite, dev)
+
+
+PTS_EXTENT_OBJECTS = 65535      # objects per launch sequence (the library's limit)
+PTS_EXTENT_POINTS = 1 << 26     # points per upload: 1.5 GiB of float64 coordinates, as much again for the pruned copy
+PTS_EXTENT_LIMIT = 1e150        # |coordinate| up to which a squared distance cannot overflow
+
+
+@functools.lru_cache(maxsize=None)
+def pts_extent_tile():
+    """Points per LDS tile of the all-pairs kernel."""
+    return int(lib().unopose_pts_extent_tile_points())
+
+
+def pts_extent(points, device, prune=True):
+    """`model_info.extent_host` for M objects (csrc/modelinfo.hip).  points: list of (V_k, 3) host arrays, 1 <= V_k <= 2^24, every
+    coordinate finite and at most 1e150 in magnitude -- checked here, before anything is launched.  -> (min (M, 3), size (M, 3) = max - min,
+    diameter (M,)), float64 host arrays; the diameter is the square root, taken on the host, of the largest (dx*dx + dy*dy) + dz*dz the
+    kernel finds, pair (i, i) included: the bits of the host route and of the toolkit's `misc.calc_pts_diameter`.  prune=True lets only the
+    points that can belong to a farthest pair into the all-pairs pass; it changes the time, not a bit of the result.  The objects go up in
+    one upload with their offsets table and are scored by one launch sequence; more than 65535 objects or 2^26 points are split into
+    several such calls.  Calling it twice gives the same bits."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("pts_extent: CPU not supported")
+    clouds = []
+    for k, p in enumerate(points):
+        p = np.asarray(p, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 3 or not 1 <= p.shape[0] <= 1 << 24:
+            raise ValueError(f"pts_extent: object {k} is {p.shape}: (V, 3) with 1 <= V <= 2^24")
+        if not (np.abs(p) <= PTS_EXTENT_LIMIT).all():  # False for NaN too
+            raise ValueError(f"pts_extent: object {k} holds a coordinate that is not finite or beyond {PTS_EXTENT_LIMIT:g}")
+        clouds.append(p)
+    if not clouds:
+        raise ValueError("pts_extent: no objects")
+    doubles = int(lib().unopose_pts_extent_doubles())
+    chunks, rows = [[]], 0
+    for p in clouds:
+        if chunks[-1] and (len(chunks[-1]) == PTS_EXTENT_OBJECTS or rows + len(p) > PTS_EXTENT_POINTS):
+            chunks.append([])
+            rows = 0
+        chunks[-1].append(p)
+        rows += len(p)
+    pending = []
+    for chunk in chunks:
+        M = len(chunk)
+        offsets = np.zeros(M + 1, dtype=np.int64)
+        np.cumsum([len(p) for p in chunk], out=offsets[1:])
+        N = int(offsets[-1])
+        host = np.empty(3 * N + M + 1, dtype=np.float64)
+        host[:3 * N] = np.concatenate([p.reshape(-1) for p in chunk])
+        host[3 * N:] = offsets.view(np.float64)
+        buf = torch.from_numpy(host).to(dev)  # one upload: the points, then the table the kernels read
+        kept = torch.empty(3 * N, dtype=torch.float64, device=dev) if prune else None
+        kept_count = torch.empty(M, dtype=torch.int64, device=dev) if prune else None
+        out = torch.empty(M, doubles, dtype=torch.float64, device=dev)
+        null = ctypes.c_void_p(None)
+        with on_device(dev):
+            call("unopose_pts_extent", ptr(buf), ctypes.c_void_p(offsets.ctypes.data), ptr(buf[3 * N:]), M, int(bool(prune)),
+                 ptr(kept) if prune else null, ptr(kept_count) if prune else null, ptr(out), stream_ptr(dev))
+        pending.append((out, buf, kept, kept_count))  # the buffers live until the read-back below
+    res = np.concatenate([p[0].cpu().numpy() for p in pending])  # read back after everything is queued
+    return res[:, :3].copy(), res[:, 3:6] - res[:, :3], np.sqrt(res[:, 6])
