@@ -715,6 +715,31 @@ int unopose_pts_extent_doubles(void);
 int unopose_pts_extent(const double *pts, const long long *offsets, const long long *offsets_dev, int M, int prune, double *kept,
                        long long *kept_count, double *out, unopose_stream_t stream);
 
+/* One-reference target lists (csrc/reftargets.hip; unopose_amd/ref_targets.py's select_host is the specification -- the project's own rule:
+ * the reference publishes the list for YCB-V and no generator).  For the Q query views and C candidate views of ONE object under its S
+ * symmetries, all float64 and every product by bop_eval._dot3: T[c,s] = R_c S_s, tr[q,c,s] = min((d0 + d1) + d2, 3) with d_r the r-th diagonal
+ * element of R_q T^T, best[q,c] = max over s.  A candidate is allowed if c_scene != q_scene (cross_scene != 0) or c_key != q_key (cross_scene
+ * = 0), eligible if allowed and best >= trace_min (= 1 + 2 cos(max rotation), computed by the caller).
+ * Rq (Q,9), Rc (C,9), syms (S,9) float64 row-major rotations; q_scene, c_scene int64; q_key, c_key uint64; all device memory.
+ * out (4,Q) int64: the pick = the eligible candidate with the smallest mix64(mix64(seed + G + q_key) + G + c_key) (splitmix64's finaliser and
+ * increment G = 0x9E3779B97F4A7C15, uint64 wrap-around; equal priorities: the lower index), -1 without one; the number of eligible candidates;
+ * the nearest = the allowed candidate with the largest best (the lower index among equals), -1 if none is allowed; the bit pattern of that
+ * best as float64 (+0.0 for a zero, -inf if none).
+ * The candidates are cut into slabs of `slab` candidates, one workgroup per (slab, tile of unopose_ref_select_query_tile() queries), walking the
+ * (candidate, symmetry) entries in LDS tiles of unopose_ref_select_entry_tile(); workspace: 5 * Q * ceil(C / slab) int64 of device memory for the
+ * per-slab partials, which a second kernel combines.  The result does not depend on `slab`.  unopose_ref_select_slab(Q, C, S) is the size that
+ * fills the device (0, with the error text set, for sizes the entry point refuses).
+ * 1 <= Q <= 2^22, 1 <= C <= 2^24, 1 <= S <= 2^16, slab * S <= 2^30, at most 65535 slabs.
+ * The entry point checks sizes and pointers, not values: the caller hands over finite entries of magnitude <= 1e100 (ops.ref_select refuses
+ * anything else on the host).  With a NaN or an overflowing entry the selection is arbitrary and differs from the host rule's -- the clamp
+ * turns a NaN trace into 3 where numpy's minimum keeps the NaN -- but no access leaves the buffers. */
+int unopose_ref_select_query_tile(void);
+int unopose_ref_select_entry_tile(void);
+int unopose_ref_select_slab(int Q, int C, int S);
+int unopose_ref_select(const double *Rq, const long long *q_scene, const unsigned long long *q_key, int Q, const double *Rc,
+                       const long long *c_scene, const unsigned long long *c_key, int C, const double *syms, int S, double trace_min,
+                       unsigned long long seed, int cross_scene, int slab, long long *workspace, long long *out, unopose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

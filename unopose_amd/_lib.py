@@ -139,6 +139,10 @@ SIGNATURES = {
     "unopose_pts_extent_tile_points": [],
     "unopose_pts_extent_doubles": [],
     "unopose_pts_extent": [_P, _P, _P, _I, _I, _P, _P, _P, _P],
+    "unopose_ref_select_query_tile": [],
+    "unopose_ref_select_entry_tile": [],
+    "unopose_ref_select_slab": [_I, _I, _I],
+    "unopose_ref_select": [_P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _D, ctypes.c_ulonglong, _I, _I, _P, _P, _P],
 }
 
 

@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "dot3.h"  // dot3_blas: bop_eval._dot3
 
 namespace unopose {
 
@@ -42,12 +43,6 @@ __device__ __forceinline__ double wave_min(double v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
   return v;
-}
-
-// One element of a 3 x 3 float64 product as bop_eval._dot3 forms it (the rounding of the BLAS product behind the recorded reference values):
-// a0 b0 rounded, then two fused multiply-adds in k order.  The explicit fma keeps that under -ffp-contract=off.
-__device__ __forceinline__ double dot3_blas(double a0, double b0, double a1, double b1, double a2, double b2) {
-  return __builtin_fma(a2, b2, __builtin_fma(a1, b1, a0 * b0));
 }
 
 // degrees between two rotations as bop_eval.re forms them: the diagonal of R_e R^T (dot3_blas), added in order, clamped, acos.

@@ -46,7 +46,7 @@ from .pose import (  # noqa: F401
 from .prep import (  # noqa: F401
     PrepPlan, _desc_ints, _tap_table, prep_norm_table, _require, _result, prep_crop_resize, prep_lift, prep_gather,
 )
-from .score import vsd_counts, pose_errors, pose_metrics, adi, gt_visibility, pts_extent  # noqa: F401
+from .score import vsd_counts, pose_errors, pose_metrics, adi, gt_visibility, pts_extent, ref_select  # noqa: F401
 from .train import (  # noqa: F401
     _InfoNCEFn, infonce_two_way, _BNReLUTrain, bn_relu, _BNReLUMaxPoolTrain, bn_relu_maxpool, _SaliencyFn, saliency_pair,
     nearest_partner, _CONV_FWD_PAIRS, _CONV_WGRAD_PAIRS, _conv1x1_pair_ok, _conv1x1_wgrad_ok, _Conv1x1Fn, conv1x1,

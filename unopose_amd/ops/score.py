@@ -2,7 +2,8 @@
 `bop_eval.mssd` / `mspd` errors, for many (estimate, ground truth) pairs per launch, and the further errors of csrc/posemetrics.hip:
 `pose_metrics` (add, proj, re, te and the symmetry-aware projS, reS, teS) and `adi`; `gt_visibility` (csrc/gtinfo.hip) is the
 ground-truth side, the integers behind `scene_gt_info.json` and the two masks; `pts_extent` (csrc/modelinfo.hip) the model side, the box
-and the diameter behind `models_info.json`.  `bop_eval`'s and `gt_info`'s host functions are the
+and the diameter behind `models_info.json`; `ref_select` (csrc/reftargets.hip) the reference-view search behind the one-reference target list
+(`ref_targets.select_host`, equal bits).  `bop_eval`'s and `gt_info`'s host functions are the
 specification: the counts equal numpy's, the distances and means agree with the BLAS-backed host code to rounding.
 
 The kernels trust the map indices they are given: the wrappers check every index against the map stacks on the host BEFORE
@@ -291,3 +292,50 @@ def pts_extent(points, device, prune=True):
         pending.append((out, buf, kept, kept_count))  # the buffers live until the read-back below
     res = np.concatenate([p[0].cpu().numpy() for p in pending])  # read back after everything is queued
     return res[:, :3].copy(), res[:, 3:6] - res[:, :3], np.sqrt(res[:, 6])
+
+
+@functools.lru_cache(maxsize=None)
+def ref_select_sizes():
+    """(queries per workgroup, (candidate, symmetry) entries per LDS tile) of the reference-selection kernel."""
+    return int(lib().unopose_ref_select_query_tile()), int(lib().unopose_ref_select_entry_tile())
+
+
+def ref_select_slab(Q, C, S):
+    """Candidates per workgroup that `ref_select` takes when `slab` is left to it."""
+    slab = int(lib().unopose_ref_select_slab(int(Q), int(C), int(S)))
+    if slab < 1:
+        raise ValueError(f"ref_select: {lib().unopose_last_error().decode()}")
+    return slab
+
+
+def ref_select(Rq, q_scene, q_key, Rc, c_scene, c_key, syms, trace_min, seed=0, cross_scene=True, device="cuda", slab=None):
+    """`ref_targets.select_host` for one object (csrc/reftargets.hip).  Rq (Q, 3, 3), Rc (C, 3, 3), syms (S >= 1, 3, 3) rotations; q_scene, c_scene
+    int64 scene identities; q_key, c_key uint64 view keys; trace_min = 1 + 2 cos(max rotation); seed: a 64-bit unsigned number -- host arrays,
+    checked by `ref_targets.check_inputs`, the host rule's own validator, before anything is launched (finite, |entry| <= 1e100), one upload.
+    -> (pick (Q,) int64, n_eligible (Q,) int64, nearest (Q,) int64, nearest_trace (Q,) float64), host arrays with the host rule's bits.
+    Q or C of zero returns empty or all -1 results without a launch.  `slab`: candidates per workgroup (default: what fills the device); the
+    result does not depend on it.  Calling it twice gives the same bits."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("ref_select: CPU not supported")
+    from ..ref_targets import check_inputs  # one validator for both routes
+
+    Rq, q_scene, q_key, Rc, c_scene, c_key, syms, trace_min, seed = check_inputs(Rq, q_scene, q_key, Rc, c_scene, c_key, syms, trace_min, seed)
+    Q, C, S = len(Rq), len(Rc), len(syms)
+    if Q == 0 or C == 0:
+        return np.full(Q, -1, np.int64), np.zeros(Q, np.int64), np.full(Q, -1, np.int64), np.full(Q, -np.inf)
+    slab = ref_select_slab(Q, C, S) if slab is None else int(slab)
+    if not 1 <= slab <= C:
+        raise ValueError(f"ref_select: {slab} candidates per slab (1 .. C = {C})")
+    host = np.concatenate([Rq.reshape(-1), Rc.reshape(-1), syms.reshape(-1), q_scene.view(np.float64), q_key.view(np.float64), c_scene.view(np.float64),
+                           c_key.view(np.float64)])
+    buf = torch.from_numpy(host).to(dev)  # one upload
+    o = np.cumsum([0, 9 * Q, 9 * C, 9 * S, Q, Q, C, C])
+    part = [buf[o[i]:o[i + 1]] for i in range(7)]
+    work = torch.empty(5 * Q * -(-C // slab), dtype=torch.int64, device=dev)
+    out = torch.empty(4, Q, dtype=torch.int64, device=dev)
+    with on_device(dev):
+        call("unopose_ref_select", ptr(part[0]), ptr(part[3]), ptr(part[4]), Q, ptr(part[1]), ptr(part[5]), ptr(part[6]), C, ptr(part[2]), S, trace_min,
+             seed, int(bool(cross_scene)), slab, ptr(work), ptr(out), stream_ptr(dev))
+    res = out.cpu().numpy()
+    return res[0].copy(), res[1].copy(), res[2].copy(), res[3].copy().view(np.float64)

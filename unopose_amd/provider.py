@@ -371,6 +371,17 @@ class _PinnedReturn:
         return view.numpy()
 
 
+def ref_split_folder(data_dir, dataset, ref_scene_id, test_folder=None):
+    """Where a reference scene lives: ycbv references outside the 12 test scenes and all tudl references come
+    from train_real (:246-251); every other one from `test_folder` (default: the dataset's test split).  The one statement of the rule:
+    the provider loads references by it and `ref_targets` builds its candidate pool by it."""
+    test_folder = osp.join(data_dir, dataset, "test") if test_folder is None else test_folder
+    train_real = osp.join(data_dir, dataset, "train_real")
+    if dataset == "ycbv":
+        return test_folder if 48 <= ref_scene_id < 60 else train_real
+    return train_real if dataset == "tudl" else test_folder
+
+
 # ------------------------------------------------------------------------------------------------
 class BOPTestsetOneRef:
     """One item = one test image: all detections above `seg_filter_score` (or the best one), each paired
@@ -582,12 +593,7 @@ class BOPTestsetOneRef:
         return self._device_image[1:]
 
     def _ref_split_folder(self, ref_scene_id):
-        """Where a reference scene lives: ycbv references outside the 12 test scenes and all tudl references come
-        from train_real (:246-251)."""
-        train_real = osp.join(self.data_dir, self.dataset, "train_real")
-        if self.dataset == "ycbv":
-            return self.data_folder if 48 <= ref_scene_id < 60 else train_real
-        return train_real if self.dataset == "tudl" else self.data_folder
+        return ref_split_folder(self.data_dir, self.dataset, ref_scene_id, self.data_folder)
 
     def _reference_instance(self, scene_id, img_id, obj_id):
         target = self.test_ref_target.get(f"{scene_id}_{img_id}_{obj_id}")
