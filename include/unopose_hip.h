@@ -740,6 +740,30 @@ int unopose_ref_select(const double *Rq, const long long *q_scene, const unsigne
                        const long long *c_scene, const unsigned long long *c_key, int C, const double *syms, int S, double trace_min,
                        unsigned long long seed, int cross_scene, int slab, long long *workspace, long long *out, unopose_stream_t stream);
 
+/* The optimiser step of the training run in three launches, whatever the number of tensors (csrc/optim.hip; unopose_amd/optim.py FusedAdam):
+ * gradient hygiene (core/unopose/engine/engine_utils.py:14-18) + the 2-norm, then torch.nn.utils.clip_grad_norm_'s coefficient and a device-side
+ * gate, then torch.optim.Adam's update (amsgrad = maximize = False).  fp32, contiguous tensors.  Device tables, built and range-checked by the caller:
+ *   grads_dev   n_tensors float32 pointers, the gradients;
+ *   state_dev   n_tensors x unopose_adam_table_ints(4) = 4 pointers: param, exp_avg, exp_avg_sq (float32) and the tensor's step count (one int32);
+ *   chunks_dev  n_chunks entries of unopose_adam_table_ints(1) = 4 int32 words: tensor index, length (1 .. chunk), then the element offset as
+ *               int64; a tensor is cut into ceil(numel / chunk) entries, chunk = unopose_adam_table_ints(0) elements, one workgroup each;
+ *   block       unopose_adam_table_ints(2) = 4 float32 [norm, clip coefficient, gate 1 / 0, unused] followed by unopose_adam_table_ints(3) = 2
+ *               per tensor [lr / (1 - beta1^t), sqrt(1 - beta2^t)]; partials: n_chunks float64.
+ * _prepare:  every gradient cleaned in place (NaN -> 0, +inf -> 1e5, -inf -> -1e5; finite values are not rewritten), partials[c] = the sum of
+ *            squares of chunk c's cleaned values in float64.  No atomics: the same bits on every run.
+ * _finalise: one workgroup.  norm = sqrt(sum of the partials in a fixed order); coefficient = min(max_norm / (norm + 1e-6), 1) in fp32
+ *            (max_norm < 0: no clipping, coefficient 1, the norm is still written).  finite: NULL or one device byte; NULL or non-zero opens the
+ *            gate: the n_tensors step counts advance by one and the per-tensor scalars are written.  Zero closes it: only block[0 .. 3] is written.
+ * _update:   param, exp_avg, exp_avg_sq of every chunk by Adam's rule with gradient * coefficient (+ weight_decay * param); the gradients are
+ *            only read.  With the gate closed no workgroup reads or writes anything else.
+ * All three enqueue on `stream`; n_chunks = 0 launches nothing in _prepare / _update. */
+int unopose_adam_table_ints(int what);
+int unopose_adam_prepare(const void *grads_dev, const void *chunks_dev, long n_chunks, int n_tensors, double *partials, unopose_stream_t stream);
+int unopose_adam_finalise(const double *partials, long n_chunks, int n_tensors, const void *state_dev, const void *finite, double max_norm, double lr,
+                          double beta1, double beta2, float *block, unopose_stream_t stream);
+int unopose_adam_update(const void *grads_dev, const void *state_dev, const void *chunks_dev, long n_chunks, int n_tensors, const float *block,
+                        double beta1, double beta2, double eps, double weight_decay, unopose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

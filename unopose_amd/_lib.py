@@ -143,6 +143,10 @@ SIGNATURES = {
     "unopose_ref_select_entry_tile": [],
     "unopose_ref_select_slab": [_I, _I, _I],
     "unopose_ref_select": [_P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _D, ctypes.c_ulonglong, _I, _I, _P, _P, _P],
+    "unopose_adam_table_ints": [_I],
+    "unopose_adam_prepare": [_P, _P, _L, _I, _P, _P],
+    "unopose_adam_finalise": [_P, _L, _I, _P, _P, _D, _D, _D, _D, _P, _P],
+    "unopose_adam_update": [_P, _P, _P, _L, _I, _P, _D, _D, _D, _D, _P],
 }
 
 

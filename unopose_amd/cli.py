@@ -141,7 +141,7 @@ def _gt_visibility(be):
     return dict(gt_visibility=mode, visib_gt_min=None if least is None else float(least), gt_delta=None if delta is None else float(delta))
 
 
-def _launch_ranks(n, argv, poll_s=0.2):
+def _launch_ranks(n, argv, poll_s=0.2, module="unopose_amd.cli"):
     """N fresh interpreters with the torchrun environment contract; the parent has not initialised HIP.  All children are polled:
     when any one exits non-zero the others are terminated and that code is returned (as torchrun does) -- a rank that dies must not
     leave the rest blocked in a collective until the watchdog fires."""
@@ -155,7 +155,7 @@ def _launch_ranks(n, argv, poll_s=0.2):
     for r in range(n):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1", MASTER_PORT=port,
                    HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-        procs.append(subprocess.Popen([sys.executable, "-m", "unopose_amd.cli"] + argv, env=env))
+        procs.append(subprocess.Popen([sys.executable, "-m", module] + argv, env=env))
     while True:
         codes = [p.poll() for p in procs]
         bad = [c for c in codes if c not in (None, 0)]

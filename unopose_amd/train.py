@@ -6,6 +6,7 @@ anneal LR multiplier.  Data parallelism is replicas + gradient all-reduce: torch
 "nccl" on ROCm), gradient buckets reduced during backward; no other collective.  The frozen DINOv2 backbone runs on the
 fused inference kernels under no_grad; everything trainable runs op-by-op under autograd (ops.differentiable)."""
 import math
+import weakref
 
 import torch
 
@@ -117,3 +118,57 @@ def train_step(model, batch, optimizer, scheduler=None, clip_max_norm=None, amp_
     if not finite:  # the reference asserts a finite loss every iteration (engine.py); a NaN step has been cleaned by the gradient hygiene above
         raise FloatingPointError(f"non-finite loss {loss.detach()}")
     return {k: v.detach() for k, v in info.items()}
+
+
+_BUFFERS = weakref.WeakKeyDictionary()  # model -> its buffers grouped by dtype (the walk over the modules is made once)
+
+
+def _snapshot_buffers(model):
+    """The model's buffers (BatchNorm's running statistics: the forward updates them in train mode) as one concatenated copy per dtype."""
+    groups = _BUFFERS.get(model)
+    if groups is None:
+        groups = {}
+        for b in model.buffers():
+            groups.setdefault((b.dtype, b.device), []).append(b)
+        groups = _BUFFERS[model] = list(groups.values())
+    return [(bufs, torch.cat([b.detach().reshape(-1) for b in bufs])) for bufs in groups]
+
+
+def _restore_buffers(saved):
+    with torch.no_grad():
+        for bufs, flat in saved:
+            for b, v in zip(bufs, flat.split([b.numel() for b in bufs])):
+                b.copy_(v.reshape(b.shape))
+
+
+def train_step_gated(model, batch, optimizer, scheduler=None, clip_max_norm=None, amp_dtype=None):
+    """`train_step` with the update gated ON THE DEVICE by the finite flag -- the loss and every other scalar of process_loss are finite --
+    (`optimizer`: an `optim.FusedAdam`): forward -> process_loss ->
+    backward -> `optimizer.step(finite, clip_max_norm)` (gradient hygiene, clipping and Adam in three launches) -> ONE host read of the flag,
+    at the end of the step like `train_step`'s.  Flag set: the scheduler advances; returns the detached scalars of process_loss plus
+    `total_grad_norm`.  Flag clear: FloatingPointError, with parameters, moments, step counts and schedule exactly as before the call; so are the
+    model's buffers (the running statistics the failed forward moved are put back from a copy taken before it: one small launch per dtype)."""
+    model.train()
+    saved = _snapshot_buffers(model)
+    with torch.autocast("cuda", dtype=amp_dtype or torch.bfloat16, enabled=amp_dtype is not None):
+        out = model(dict(batch))
+        info = process_loss(out)
+    loss = info["loss"]
+    # The flag covers every scalar of process_loss, not the loss alone: a NaN or inf in a LABEL never reaches the loss -- the labels enter it only
+    # through comparisons (nearest partner within a threshold), which a NaN fails silently -- but it does reach the `*_dis` monitors.
+    finite = torch.isfinite(torch.stack([v.detach().float().reshape(()) for v in info.values()])).all().reshape(1)
+    optimizer.zero_grad(set_to_none=True)
+    loss.backward()
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        finite = finite.to(torch.uint8)  # one gate for all replicas: they share the gradients, so they update together or not at all
+        torch.distributed.all_reduce(finite, op=torch.distributed.ReduceOp.MIN)
+    norm = optimizer.step(finite, clip_max_norm)
+    if not finite:  # the step's only host wait
+        _restore_buffers(saved)
+        bad = [k for k, v in info.items() if not bool(torch.isfinite(v.detach()).all())]
+        raise FloatingPointError(f"non-finite loss {loss.detach()}; non-finite scalars of the step: {bad or 'on another rank'}")
+    if scheduler is not None:
+        scheduler.step()
+    info = {k: v.detach() for k, v in info.items()}
+    info["total_grad_norm"] = norm
+    return info
