@@ -501,6 +501,37 @@ int unopose_linear_attention_f32(const float *x, const float *inv_softplus_scale
 int unopose_render_depth(const float *verts, int V, const int *faces, int F, const float *Rt, const float *K4, int P, int H, int W,
                          float *depth, unopose_stream_t stream);
 
+/* Colour and depth of a triangle mesh in P poses, for the pose visualisation (csrc/raster_color.hip; the renderer.render_object(...)["rgb"],
+ * ["depth"] that third_party/bop_toolkit/bop_toolkit_lib/visualization.py:93-235 draws).  verts, faces, Rt, K4 as for unopose_render_depth;
+ * depth (P,H,W) float32 carries the bits unopose_render_depth writes for the same inputs.  A pixel belongs to the nearest face and, at equal
+ * depth, to the face of the lowest index: keys (P*H*W 64-bit words of device memory, 8-byte aligned, a workspace) holds
+ * (depth bits << 32) | face index under a 64-bit atomicMin.  rgb (P,H,W,3) uint8 = (int)(clamp(w c, 0, 1) 255 + 0.5), 0 where nothing projects:
+ * c = (surf_r, surf_g, surf_b) used as is when colors is NULL, else the per-vertex colors (V,3) float32 in [0,1] interpolated
+ * perspective-correctly; w = min(1, ambient + |n . Pc| / (|n| |Pc|)), the toolkit's flat shading with the light at the camera origin: n the
+ * cross product of the face's camera-space edges, Pc = ((x - cx) / fx z, (y - cy) / fy z, z); the cosine of a face with |n| |Pc| = 0 is 0.
+ * All float32, no contraction; tests/raster_rgb_np.py is the same arithmetic in numpy.  H * W <= 2^30. */
+int unopose_render_color(const float *verts, int V, const int *faces, int F, const float *colors, float surf_r, float surf_g, float surf_b,
+                         float ambient, const float *Rt, const float *K4, int P, int H, int W, void *keys, float *depth, void *rgb,
+                         unopose_stream_t stream);
+
+/* One image of the pose visualisation from the renders of its P poses (csrc/vis.hip; visualization.py:93-235 `vis_object_poses`, every cast
+ * and evaluation order kept).  rgbs (P,H,W,3) uint8 and depths (P,H,W) float32 in pose order, photo (H,W,3) uint8.
+ * _vis_compose: boxes (P,4) int32 = min x, min y, max x, max y of the pixels of a pose with any colour channel > 0 (INT_MAX, INT_MAX, INT_MIN,
+ *     INT_MIN for a pose that draws nothing); ren_depth (H,W) = depth of the nearest pose (0: none); ren_rgb (H,W,3) = with resolve_visib != 0
+ *     the colour of the nearest pose, the earliest at equal depth, else the saturating sum of all renders; vis_rgb (H,W,3) =
+ *     0.5 photo + 0.5 ren_rgb + info in float32, above 255 -> 255, truncated, where info is 76 on the 1-pixel outline of every box (corners inclusive).
+ * _vis_depth_diff: depth (H,W) float32, the captured depth in mm.  valid = depth > 0 && ren_depth > 0; diff = valid * (ren_depth - depth);
+ *     image (H,W,3) uint8: 0 at invalid pixels, else red = 255 where diff < delta, green = blue = (uint8)(255 ((s - lo) / ((hi - lo) / 0.8) + 0.2))
+ *     in float64 where s = diff - min(diff over the image) > 0 and lo, hi = minimum, maximum of the positive s over the image; 0 where s = 0.
+ *     No positive s, or hi = lo: green = blue = 51 at every valid pixel (the toolkit is undefined there).  stats (4 float64, device memory) =
+ *     minimum, maximum and mean of diff over the valid pixels (the sum in float64) and their number; all 0 without a valid pixel.
+ *     workspace: unopose_vis_workspace_ints() int32 of device memory on an 8-byte boundary. */
+int unopose_vis_workspace_ints(void);
+int unopose_vis_compose(const void *rgbs, const float *depths, int P, int H, int W, const void *photo, int resolve_visib, int *boxes,
+                        void *ren_rgb, float *ren_depth, void *vis_rgb, unopose_stream_t stream);
+int unopose_vis_depth_diff(const float *ren_depth, const float *depth, int H, int W, float delta, void *workspace, void *image, double *stats,
+                           unopose_stream_t stream);
+
 /* ---- data-movement glue of the forward as single-pass kernels (csrc/glue.hip) ---------------------------------------------
  * patchify: the ViT's 14 x 14 / 14 patch unfolding (timm PatchEmbed, oneref_feature_extraction.py:24-27) of two image batches
  * (na + nb crops of (3,S,S) float32; rgb_b may be NULL with nb = 0) into the bf16 matrix ((na + nb) (S/14)^2, Kp) the

@@ -108,6 +108,10 @@ SIGNATURES = {
     "unopose_token_sum_bf16": [_P, _I, _I, _I, _P, _P],
     "unopose_pose_score": [_P, _P, _I, _I, _F, _P, _P],
     "unopose_render_depth": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P],
+    "unopose_render_color": [_P, _I, _P, _I, _P, _F, _F, _F, _F, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "unopose_vis_workspace_ints": [],
+    "unopose_vis_compose": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P],
+    "unopose_vis_depth_diff": [_P, _P, _I, _I, _F, _P, _P, _P, _P],
     "unopose_bmm_f32": [_P, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, _P, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, _P, _I, _I, _I, _I, _I, _F, _P],
     "unopose_split_bf16x2": [_P, ctypes.c_long, _I, _P, _P],
     "unopose_linear_f32x3": [_P, _P, _P, _P, _P, ctypes.c_long, _I, _I, _I, _P],

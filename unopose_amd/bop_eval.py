@@ -800,6 +800,17 @@ def read_ply(path):
     """A PLY mesh, ASCII or binary_little_endian, with scalar vertex properties (x, y, z among them) and triangular faces (one list
     property, `vertex_indices` / `vertex_index`) -> {"pts" (V,3) float64, "faces" (F,3) int32}.  Elements other than vertex and face may
     follow them and are not read; anything else in the file is an error, not a guess."""
+    return _read_ply(path, False)
+
+
+def read_ply_colors(path):
+    """`read_ply` plus "colors": the vertex properties `red`, `green`, `blue` as (V,3) float64 in [0, 1] -- an integer property divided by
+    its type's largest value (uchar: 255, as the toolkit's renderers do), a floating-point one clipped to [0, 1] -- or None where the
+    file has no such properties (BOP's models_eval meshes carry none)."""
+    return _read_ply(path, True)
+
+
+def _read_ply(path, with_colors):
     with open(path, "rb") as f:
         data = f.read()
     end = data.find(b"end_header")
@@ -856,6 +867,12 @@ def read_ply(path):
                 raise ValueError(f"{path}: a face that is not a triangle")
         if name == "vertex":
             out["pts"] = np.stack([np.asarray(rec[k], np.float64) for k in "xyz"], axis=1)
+            if with_colors:
+                kinds = {p[1]: np.dtype(_PLY_TYPES[p[0]]) for p in props}
+                out["colors"] = None
+                if {"red", "green", "blue"} <= set(kinds):
+                    chans = [np.asarray(rec[k], np.float64) / (np.iinfo(kinds[k]).max if kinds[k].kind in "iu" else 1.0) for k in ("red", "green", "blue")]
+                    out["colors"] = np.clip(np.stack(chans, axis=1), 0.0, 1.0)
         else:
             out["faces"] = np.asarray(rec["v"]).astype(np.int32).reshape(count, 3)
     if "pts" not in out:

@@ -39,6 +39,8 @@
   exists.  Any other value is an error before any GPU work.
 * extras beyond the reference's line: ``--pipeline`` (two forwards in flight), ``--ref-cache`` (reference views encoded once),
   ``--device-prep`` (the provider builds each image's query crops, clouds and pixel indices on the rank's GPU: same items, same rows),
+  ``--vis [DIR]`` (after the CSV is written rank 0 draws its estimates over the test images with ``unopose_amd.vis_poses`` -- the selection of
+  ``bop_eval.n_top``, the dataset folder of ``--eval`` -- into DIR, by default ``vis/`` beside the CSV),
   ``--print-plan`` (resolve config and paths, touch no GPU: used by the CPU tests)."""
 import argparse
 import ast
@@ -198,9 +200,13 @@ def main(argv=None):
     ap.add_argument("--device-prep", action="store_true", help="build the query side of every item on the GPU (provider device path)")
     ap.add_argument("--eval", action="store_true", help="score the CSV after saving (BOP'19 AR; rank 0, on its GPU)")
     ap.add_argument("--eval-device-off", action="store_true", help="with --eval: compute the pose errors on the host (same renders), for comparison")
+    ap.add_argument("--vis", nargs="?", const="", default=None, metavar="DIR",
+                    help="draw the saved estimates over the test images after saving (unopose_amd.vis_poses; rank 0, on its GPU); DIR defaults to vis/ beside the CSV")
     ap.add_argument("--print-plan", action="store_true")
     ap.add_argument("opts", nargs="*", help="key=value overrides")
     args = ap.parse_args(argv)
+    if args.vis and "=" in args.vis:  # `--vis key=value`: an override, not a folder
+        args.opts, args.vis = [args.vis] + list(args.opts), ""
     cfg = apply_overrides(load_config(args.config_file), args.opts)
     out_dir, save_path = result_paths(cfg)
     c = Cfg(cfg)
@@ -231,6 +237,8 @@ def main(argv=None):
                 plan.update(eval_gt_delta=ev["gt_delta"])
             if ev["models_info"] is not None:
                 plan.update(eval_models_info=ev["models_info"])
+        if args.vis is not None:
+            plan.update(vis_dir=args.vis or osp.join(out_dir, "vis"))
         print(json.dumps(plan))
         return 0
     if not osp.exists(c.misc.load_from):  # save_unopose.sh:15-18
@@ -309,6 +317,13 @@ def main(argv=None):
                                                                   " ".join("%.4f" % v for v in blk["recalls"]), blk["mean_recall"]))
         if "errors" in sc:
             print(format_error_table(sc["errors"]))
+    if args.vis is not None and int(os.environ.get("RANK", "0")) == 0:
+        from .vis_poses import vis_dataset
+
+        ev = eval_settings(cfg)
+        shown = vis_dataset(ev["root"], ev["name"], ev["split"], results=save_path, targets_filename=ev["targets_filename"], n_top=ev["n_top"],
+                            out_dir=args.vis or osp.join(out_dir, "vis"), device=dev)
+        print(f"{len(shown)} visualisation files -> {args.vis or osp.join(out_dir, 'vis')}")
     if world > 1:
         dist.destroy_process_group()
     return 0

@@ -6,6 +6,7 @@
     pose       similarity, assignment, coarse / fine pose heads
     prep       query-side instance preparation of the BOP test provider (crops, clouds, pixel indices)
     score      pose errors of the BOP'19 scorer (VSD counts, MSSD / MSPD) for many (estimate, ground truth) pairs per launch
+    vis        per-image composition of the pose visualisation (nearest-pose layer, boxes, blend, depth-difference image)
     train      autograd Functions of the training step
 Each function cites the reference Python it replaces.  Inputs must be CUDA tensors; there is no CPU path (RuntimeError).
 `from unopose_amd import ops; ops.linear(...)` keeps working as before the split; the A/B switches (ops.USE_LN_FOLD = False, ...) live in
@@ -47,6 +48,7 @@ from .prep import (  # noqa: F401
     PrepPlan, _desc_ints, _tap_table, prep_norm_table, _require, _result, prep_crop_resize, prep_lift, prep_gather,
 )
 from .score import vsd_counts, pose_errors, pose_metrics, adi, gt_visibility, pts_extent, ref_select  # noqa: F401
+from .vis import compose_poses  # noqa: F401
 from .train import (  # noqa: F401
     _InfoNCEFn, infonce_two_way, _BNReLUTrain, bn_relu, _BNReLUMaxPoolTrain, bn_relu_maxpool, _SaliencyFn, saliency_pair,
     nearest_partner, _CONV_FWD_PAIRS, _CONV_WGRAD_PAIRS, _conv1x1_pair_ok, _conv1x1_wgrad_ok, _Conv1x1Fn, conv1x1,
