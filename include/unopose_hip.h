@@ -676,6 +676,34 @@ int unopose_prep_distances(const int *desc, const double *cloud, const double *r
 int unopose_prep_gather(const int *sel, const int *index, const int *pix, const double *cloud, int P, int n, int S, float *pts, void *choose,
                         unopose_stream_t stream);
 
+/* COCO run-length masks, both directions, for D masks of one size H x W (H * W < 2^31) per launch (csrc/rle.hip; unopose_amd/provider.py's
+ * rle_counts_from_string / rle_decode / rle_encode are the specification, i.e. pycocotools' maskApi.c rleFrString / rleDecode and the BOP
+ * toolkit's pycoco_utils.binary_mask_to_rle / bbox_from_binary_mask).  Runs alternate 0s / 1s from 0s in column-major order.
+ * desc: unopose_rle_desc_ints() int32 per mask or window, laid out as csrc/rle.hip documents; the caller has range-checked them.
+ * _rle_parse: bytes (all compressed strings back to back, every byte in 48..111) and lists (all uncompressed count lists back to back) ->
+ *     starts: per mask its n + 1 run starts (exclusive prefix sum of its counts after delta resolution, clamped to [0, H * W]) and the
+ *     initial row of stats (D, unopose_rle_stats_ints() = 6) int32 = n_set, y_first, y_last + 1, x_first, x_last + 1, flags
+ *     (1: a negative count, 2: counts summing above H * W, 4: a number without end or outside int32).
+ * _rle_fill: masks (D, H, W) uint8 in {0, 1}, row-major, every byte written; with depth (H, W) float64 (may be null) the run-length mask AND
+ *     depth > 0; adds the count and extents of the written mask to stats (an empty mask keeps y_first = H, x_first = W, the others 0).
+ * _rle_column_scan: masks (D, H, W) bytes, non-zero = set -> col_count (D, W) int32 boundaries per column and totals (D, 6) int32, ZERO before
+ *     the launch: boundaries, area, H - y_first, y_last + 1, W - x_first, x_last + 1.  A mask's count list has boundaries + 1 entries.
+ * _rle_compact: off (D + 1) int64 = start of every mask's count list in the output -> pos: its boundary positions in order (the last slot of a
+ *     mask is left alone).  _rle_diff: counts = differences of the positions, the first against 0, the last = H * W - the last position.
+ * _window_masks: K windows (desc: mask number, y0, x0, h, w, start of its bytes, start of its rows) of masks (., H, W) -> packed: the windows'
+ *     0 / 1 bytes back to back (the layout _prep_* reads), row_counts: set pixels per window row. */
+int unopose_rle_desc_ints(void);
+int unopose_rle_stats_ints(void);
+int unopose_rle_parse(const void *bytes, const int *lists, const int *desc, int D, int H, int W, int *starts, int *stats,
+                      unopose_stream_t stream);
+int unopose_rle_fill(const int *desc, const int *starts, const double *depth, int D, int H, int W, void *masks, int *stats,
+                     unopose_stream_t stream);
+int unopose_rle_column_scan(const void *masks, int D, int H, int W, int *col_count, int *totals, unopose_stream_t stream);
+int unopose_rle_compact(const void *masks, const int *col_count, const void *off, int D, int H, int W, int *pos, unopose_stream_t stream);
+int unopose_rle_diff(const int *pos, const void *off, int D, int max_n, int H, int W, int *counts, unopose_stream_t stream);
+int unopose_window_masks(const void *masks, const int *desc, int K, int max_h, int H, int W, void *packed, int *row_counts,
+                         unopose_stream_t stream);
+
 /* Pose errors of the BOP'19 scorer for P (estimate, ground truth) pairs per launch (csrc/bopscore.hip; unopose_amd/bop_eval.py's vsd / mssd /
  * mspd are the specification, i.e. bop_toolkit_lib/pose_error.py:17-101, :104-153 with visibility.py:30-70 and misc.py:142-162).
  * _vsd_counts: test (n_test,H,W), gt (n_gt,H,W), est (n_est,H,W) float32 depth maps (mm; the last two straight from unopose_render_depth);

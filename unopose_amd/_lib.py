@@ -131,6 +131,14 @@ SIGNATURES = {
     "unopose_prep_compact_lift": [_P, _I, _I, _P, _P, _P, _D, _D, _D, _D, _I, _I, _P, _P, _P, _P],
     "unopose_prep_distances": [_P, _P, _P, _I, _I, _P, _P],
     "unopose_prep_gather": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "unopose_rle_desc_ints": [],
+    "unopose_rle_stats_ints": [],
+    "unopose_rle_parse": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "unopose_rle_fill": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "unopose_rle_column_scan": [_P, _I, _I, _I, _P, _P, _P],
+    "unopose_rle_compact": [_P, _P, _P, _I, _I, _I, _P, _P],
+    "unopose_rle_diff": [_P, _P, _I, _I, _I, _I, _P, _P],
+    "unopose_window_masks": [_P, _P, _I, _I, _I, _I, _P, _P, _P],
     "unopose_vsd_count_ints": [],
     "unopose_vsd_counts": [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "unopose_pose_errors": [_P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P],

@@ -39,6 +39,7 @@
   exists.  Any other value is an error before any GPU work.
 * extras beyond the reference's line: ``--pipeline`` (two forwards in flight), ``--ref-cache`` (reference views encoded once),
   ``--device-prep`` (the provider builds each image's query crops, clouds and pixel indices on the rank's GPU: same items, same rows),
+  ``--device-masks`` (with it: the detections' run-length masks are decoded there as well),
   ``--vis [DIR]`` (after the CSV is written rank 0 draws its estimates over the test images with ``unopose_amd.vis_poses`` -- the selection of
   ``bop_eval.n_top``, the dataset folder of ``--eval`` -- into DIR, by default ``vis/`` beside the CSV),
   ``--print-plan`` (resolve config and paths, touch no GPU: used by the CPU tests)."""
@@ -198,6 +199,8 @@ def main(argv=None):
     ap.add_argument("--pipeline", action="store_true")
     ap.add_argument("--ref-cache", action="store_true")
     ap.add_argument("--device-prep", action="store_true", help="build the query side of every item on the GPU (provider device path)")
+    ap.add_argument("--device-masks", action="store_true",
+                    help="with --device-prep: decode the detections' run-length masks on the GPU as well (same items)")
     ap.add_argument("--eval", action="store_true", help="score the CSV after saving (BOP'19 AR; rank 0, on its GPU)")
     ap.add_argument("--eval-device-off", action="store_true", help="with --eval: compute the pose errors on the host (same renders), for comparison")
     ap.add_argument("--vis", nargs="?", const="", default=None, metavar="DIR",
@@ -205,6 +208,8 @@ def main(argv=None):
     ap.add_argument("--print-plan", action="store_true")
     ap.add_argument("opts", nargs="*", help="key=value overrides")
     args = ap.parse_args(argv)
+    if args.device_masks and not args.device_prep:
+        ap.error("--device-masks requires --device-prep")
     if args.vis and "=" in args.vis:  # `--vis key=value`: an override, not a folder
         args.opts, args.vis = [args.vis] + list(args.opts), ""
     cfg = apply_overrides(load_config(args.config_file), args.opts)
@@ -219,6 +224,8 @@ def main(argv=None):
         plan = dict(save_path=save_path, dataset=c.dataloader.test.dataset.eval_dataset_name, checkpoint=c.misc.load_from,
                     amp=bool(c.test.amp.enabled), instance_batch_size=c.test.instance_batch_size, num_gpus=args.num_gpus,
                     device_prep=bool(args.device_prep), eval=bool(args.eval))
+        if args.device_masks:
+            plan.update(device_masks=True)
         if args.eval:
             from .bop_eval import dataset_paths
 
@@ -274,7 +281,7 @@ def main(argv=None):
         broadcast_module_(model, src=0)
     dcfg = dict(cfg["dataloader"]["test"]["dataset"])
     name, det_path = dcfg.pop("eval_dataset_name"), dcfg.pop("detetion_path", None)
-    dataset = BOPTestsetOneRef(dcfg.get("cfg", dcfg), name, det_path, device=dev if args.device_prep else None)
+    dataset = BOPTestsetOneRef(dcfg.get("cfg", dcfg), name, det_path, device=dev if args.device_prep else None, device_masks=bool(args.device_masks))
 
     class Images:  # batch dim 1, like DataLoader(batch_size=1) over the dataset
         dets = getattr(dataset, "dets", None)

@@ -67,26 +67,76 @@ class PrepPlan:
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("PrepPlan: CPU not supported")
-        H, W = (int(v) for v in image_hw)
-        S, D = int(img_size), len(windows)
-        if D < 1 or D != len(masks) or D > 65535:
-            raise ValueError(f"PrepPlan: {D} windows, {len(masks)} masks")
-        if not 1 <= S <= 4096:
-            raise ValueError(f"PrepPlan: img_size {S}")
-        nd = _desc_ints()
-        desc = np.zeros((D, nd), dtype=np.int64)
-        flat, bases, taps, tap_at = [], [], [], {}
-        mask_off = pt_off = row_off = tap_off = 0
-        for d, (win, mask) in enumerate(zip(windows, masks)):
-            y0, y1, x0, x1 = (int(v) for v in (win.as_list() if hasattr(win, "as_list") else win))
+        if len(windows) != len(masks):
+            raise ValueError(f"PrepPlan: {len(windows)} windows, {len(masks)} masks")
+        boxes = self._boxes(image_hw, windows, img_size)
+        flat, rows = [], []
+        for (y0, y1, x0, x1), mask in zip(boxes, masks):
             h, w = y1 - y0, x1 - x0
-            if not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
-                raise ValueError(f"PrepPlan: window {(y0, y1, x0, x1)} outside the {H} x {W} image")
             m = np.ascontiguousarray(np.asarray(mask) != 0)
             if m.shape != (h, w):
                 raise ValueError(f"PrepPlan: mask {m.shape} for a {h} x {w} window")
-            rows = m.sum(axis=1, dtype=np.int64)
-            n = int(rows.sum())
+            flat.append(m.reshape(-1))
+            rows.append(m.sum(axis=1, dtype=np.int64))
+        self._assemble(image_hw, boxes, rows, img_size, device)
+        self.masks = torch.from_numpy(np.concatenate(flat).view(np.uint8)).to(device)
+
+    @classmethod
+    def from_device(cls, image_hw, windows, packed_masks, row_counts, img_size, device):
+        """The same plan from window masks that are already on the device (`ops.window_masks`): `packed_masks` = the windows' 0 / 1
+        bytes back to back in window order (kept, not copied), `row_counts` = their set pixels per row in the same order, int32 on the
+        device (read back here in one pinned copy) or already on the host."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("PrepPlan: CPU not supported")
+        boxes = cls._boxes(image_hw, windows, img_size)
+        heights = [y1 - y0 for y0, y1, _, _ in boxes]
+        _require(packed_masks, "PrepPlan: packed_masks", torch.uint8, (sum((y1 - y0) * (x1 - x0) for y0, y1, x0, x1 in boxes),))
+        if torch.is_tensor(row_counts):
+            _require(row_counts, "PrepPlan: row_counts", torch.int32, (sum(heights),))
+            from .rle import _to_host
+
+            with torch.cuda.device(device):
+                row_counts = _to_host(row_counts)
+        row_counts = np.asarray(row_counts).reshape(-1).astype(np.int64)
+        if len(row_counts) != sum(heights):
+            raise ValueError(f"PrepPlan: {len(row_counts)} row counts for {sum(heights)} window rows")
+        widths = np.repeat([x1 - x0 for _, _, x0, x1 in boxes], heights)
+        if (row_counts < 0).any() or (row_counts > widths).any():
+            raise ValueError("PrepPlan: row count outside its window row")
+        plan = cls.__new__(cls)
+        plan._assemble(image_hw, boxes, np.split(row_counts, np.cumsum(heights)[:-1]), img_size, device)
+        plan.masks = packed_masks
+        return plan
+
+    @staticmethod
+    def _boxes(image_hw, windows, img_size):
+        """The windows as (y0, y1, x0, x1) integers, checked against the image."""
+        H, W = (int(v) for v in image_hw)
+        S, D = int(img_size), len(windows)
+        if D < 1 or D > 65535:
+            raise ValueError(f"PrepPlan: {D} windows")
+        if not 1 <= S <= 4096:
+            raise ValueError(f"PrepPlan: img_size {S}")
+        boxes = []
+        for win in windows:
+            y0, y1, x0, x1 = (int(v) for v in (win.as_list() if hasattr(win, "as_list") else win))
+            if not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+                raise ValueError(f"PrepPlan: window {(y0, y1, x0, x1)} outside the {H} x {W} image")
+            boxes.append((y0, y1, x0, x1))
+        return boxes
+
+    def _assemble(self, image_hw, boxes, rows, img_size, device):
+        """Descriptors, row prefixes and tap tables from the checked windows and their per-row set counts; one upload."""
+        H, W = (int(v) for v in image_hw)
+        S, D = int(img_size), len(boxes)
+        nd = _desc_ints()
+        desc = np.zeros((D, nd), dtype=np.int64)
+        bases, taps, tap_at = [], [], {}
+        mask_off = pt_off = row_off = tap_off = 0
+        for d, ((y0, y1, x0, x1), row) in enumerate(zip(boxes, rows)):
+            h, w = y1 - y0, x1 - x0
+            n = int(row.sum())
             if n < 1:
                 raise ValueError("PrepPlan: empty mask")
             mode = 0 if (h, w) == (S, S) else 1 if (h, w) == (2 * S, 2 * S) else 2
@@ -99,8 +149,7 @@ class PrepPlan:
                         tap_off += 4 * S
                     at[axis] = tap_at[(src, axis)]
             desc[d, :11] = (y0, x0, h, w, mask_off, pt_off, n, row_off, mode, at[0], at[1])
-            flat.append(m.reshape(-1))
-            bases.append(np.cumsum(rows) - rows)
+            bases.append(np.cumsum(row) - row)
             mask_off, pt_off, row_off = mask_off + h * w, pt_off + n, row_off + h
         if max(mask_off, 3 * pt_off, tap_off) >= 2 ** 31:
             raise ValueError("PrepPlan: too many pixels for 32-bit offsets")
@@ -108,7 +157,6 @@ class PrepPlan:
         ints_dev = torch.from_numpy(ints).to(device)
         self.desc, self.row_base = ints_dev[:D * nd], ints_dev[D * nd:D * nd + row_off]
         self.taps = ints_dev[D * nd + row_off:] if taps else ints_dev[:1]  # never read without bilinear windows
-        self.masks = torch.from_numpy(np.concatenate(flat).view(np.uint8)).to(device)
         self.device, self.H, self.W, self.S, self.D = device, H, W, S, D
         self.h, self.w, self.n, self.pt_off = (desc[:, c].copy() for c in (2, 3, 6, 5))
         self.n_points, self.n_rows = pt_off, row_off

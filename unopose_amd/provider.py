@@ -141,10 +141,15 @@ class Window:
 
     @classmethod
     def around(cls, mask):
-        H, W = mask.shape
         ys = np.flatnonzero(mask.any(axis=1))
         xs = np.flatnonzero(mask.any(axis=0))
-        top, bottom, left, right = ys[0], ys[-1] + 1, xs[0], xs[-1] + 1  # half-open extents
+        return cls.from_extents(mask.shape, ys[0], ys[-1] + 1, xs[0], xs[-1] + 1)
+
+    @classmethod
+    def from_extents(cls, image_hw, top, bottom, left, right):
+        """The window around a mask of an (H, W) image whose set pixels span rows [top, bottom) and columns [left, right)."""
+        H, W = image_hw
+        top, bottom, left, right = int(top), int(bottom), int(left), int(right)  # half-open extents
         half = int(min(max(bottom - top, right - left), min(H, W)) / 2)
         cy, cx = int((top + bottom) / 2), int((left + right) / 2)
         y0, x0 = cy - half, cx - half
@@ -396,10 +401,15 @@ class BOPTestsetOneRef:
 
     `device`: a CUDA device turns on the device path of the query side: the per-pixel work of all detections of an image runs
     in HIP kernels (ops/prep.py) and the item's `pts`, `rgb` and `rgb_choose` are tensors on that device, equal to the host
-    path's; every other key, the ``np.random`` stream and the control flow are the host path's (:meth:`_instances_device`)."""
+    path's; every other key, the ``np.random`` stream and the control flow are the host path's (:meth:`_instances_device`).
+    `device_masks` (with `device`): the detections' run-length masks are decoded on the device as well (ops/rle.py): one decode for all
+    detections of an image against the resident depth map, so that no mask is built on the host or uploaded; same items."""
 
-    def __init__(self, cfg, eval_dataset_name="lmo", detetion_path=None, device=None):
+    def __init__(self, cfg, eval_dataset_name="lmo", detetion_path=None, device=None, device_masks=False):
         assert detetion_path is not None
+        if device_masks and device is None:
+            raise ValueError("BOPTestsetOneRef: device_masks needs `device`")
+        self.device_masks = bool(device_masks)
         self.device = None if device is None else torch.device(device)
         if self.device is not None and self.device.type != "cuda":
             raise RuntimeError("BOPTestsetOneRef: device preparation on CPU not supported (leave `device` unset for the host path)")
@@ -529,21 +539,33 @@ class BOPTestsetOneRef:
         from .ops import prep
 
         cands = []  # (detection number, detection, window, window mask)
-        for i in order:
-            det = dets[i]
-            K, depth_scale = self.files.camera(self.data_folder, det["scene_id"], det["image_id"])
-            depth = self.files.depth_m(self.data_folder, det["scene_id"], det["image_id"], depth_scale)
-            valid = np.logical_and(rle_decode(det["segmentation"]) > 0, depth > 0)
-            if not np.sum(valid) > self.minimum_n_point:
-                continue  # None before any draw
-            win = Window.around(valid)
-            cands.append((i, det, win, win.crop(valid)))
+        if self.device_masks:
+            if not order:
+                return None
+            cands, K, depth, masks_dev = self._candidates_device(dets, order)
+        else:
+            for i in order:
+                det = dets[i]
+                K, depth_scale = self.files.camera(self.data_folder, det["scene_id"], det["image_id"])
+                depth = self.files.depth_m(self.data_folder, det["scene_id"], det["image_id"], depth_scale)
+                valid = np.logical_and(rle_decode(det["segmentation"]) > 0, depth > 0)
+                if not np.sum(valid) > self.minimum_n_point:
+                    continue  # None before any draw
+                win = Window.around(valid)
+                cands.append((i, det, win, win.crop(valid)))
         if not cands:
             return None  # nothing was uploaded or launched
         scene_id, img_id = cands[0][1]["scene_id"], cands[0][1]["image_id"]  # `dets` are one image's
         with torch.cuda.device(self.device):
             colour_dev, depth_dev = self._image_on_device(scene_id, img_id, depth)
-            plan = prep.PrepPlan(depth.shape, [c[2] for c in cands], [c[3] for c in cands], self.img_size, self.device)
+            if self.device_masks:
+                from .ops import rle
+
+                wins = [c[2] for c in cands]
+                packed, row_counts = rle.window_masks(masks_dev, wins, [c[3] for c in cands])
+                plan = prep.PrepPlan.from_device(depth.shape, wins, packed, row_counts, self.img_size, self.device)
+            else:
+                plan = prep.PrepPlan(depth.shape, [c[2] for c in cands], [c[3] for c in cands], self.img_size, self.device)
             pix, cloud, dist = prep.prep_lift(depth_dev, K, plan)
             pending = self._distances.start(dist)
             crops = prep.prep_crop_resize(colour_dev, plan, bgr=self.rgb_to_bgr, use_mask=self.rgb_mask_flag)  # runs under the host's walk
@@ -583,6 +605,36 @@ class BOPTestsetOneRef:
                 crops = crops[torch.as_tensor(slots, device=self.device)]
         return ids, insts, {"pts": pts, "rgb": crops, "rgb_choose": choose}
 
+    def _candidates_device(self, dets, order):
+        """The candidate list of :meth:`_instances_device` with the masks decoded on the device: one decode of the run-length masks of
+        `order` against the resident depth (`valid` of get_instance), one readback of their counts and extents; the host applies the
+        minimum-count rule and builds the windows -> ([(detection number, detection, window, mask number)], K, depth, masks)."""
+        from .ops import rle
+
+        first = dets[order[0]]
+        scene_id, img_id = first["scene_id"], first["image_id"]  # `dets` are one image's
+        K, depth_scale = self.files.camera(self.data_folder, scene_id, img_id)
+        depth = self.files.depth_m(self.data_folder, scene_id, img_id, depth_scale)
+        with torch.cuda.device(self.device):
+            masks, _, stats = rle.rle_decode([dets[i]["segmentation"] for i in order], self.device, self._depth_on_device(scene_id, img_id, depth),
+                                             with_host_stats=True)
+        if tuple(masks.shape[1:]) != depth.shape:
+            raise ValueError(f"segmentation size {tuple(masks.shape[1:])} for a {depth.shape} image")
+        cands = []
+        for slot, i in enumerate(order):
+            n, top, bottom, left, right = (int(v) for v in stats[slot, :5])
+            if not n > self.minimum_n_point:
+                continue  # None before any draw
+            cands.append((i, dets[i], Window.from_extents(depth.shape, top, bottom, left, right), slot))
+        return cands, K, depth, masks
+
+    def _depth_on_device(self, scene_id, img_id, depth):
+        """The depth half of :meth:`_image_on_device` alone: the colour image follows only when a detection survives."""
+        key = (scene_id, img_id)
+        if self._device_image is None or self._device_image[0] != key:
+            self._device_image = (key, None, torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float64)).to(self.device))
+        return self._device_image[2]
+
     def _image_on_device(self, scene_id, img_id, depth):
         """Colour (uint8) and depth (float64 metres: float32 would not give the host path's bits) of the image, uploaded once."""
         key = (scene_id, img_id)
@@ -590,6 +642,9 @@ class BOPTestsetOneRef:
             colour = np.ascontiguousarray(self.files.colour(self.data_folder, scene_id, img_id))
             self._device_image = (key, torch.from_numpy(colour).to(self.device),
                                   torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float64)).to(self.device))
+        elif self._device_image[1] is None:  # the depth went up alone for the mask decode
+            colour = np.ascontiguousarray(self.files.colour(self.data_folder, scene_id, img_id))
+            self._device_image = (key, torch.from_numpy(colour).to(self.device), self._device_image[2])
         return self._device_image[1:]
 
     def _ref_split_folder(self, ref_scene_id):
