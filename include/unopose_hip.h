@@ -823,6 +823,25 @@ int unopose_adam_finalise(const double *partials, long n_chunks, int n_tensors, 
 int unopose_adam_update(const void *grads_dev, const void *state_dev, const void *chunks_dev, long n_chunks, int n_tensors, const float *block,
                         double beta1, double beta2, double eps, double weight_decay, unopose_stream_t stream);
 
+/* The training provider's colour augmentation (unopose_amd/provider_train.py: ColorAugmentor.apply is the specification; results equal it
+ * byte for byte) for n_crops crops of one uint8 HWC atlas (H rows of W pixels, 3 channels; crop c on rows y0 .. y0 + h - 1, columns 0 .. w - 1,
+ * the rest of its rows is padding nobody touches).  desc: unopose_coloraug_ints(0) int32 per crop, ops: unopose_coloraug_ints(1) int32 per
+ * chain entry, both laid out as csrc/coloraug.hip documents; the caller has range-checked them.  grids: the coarse-dropout grids (bytes),
+ * noise: the noise fields (float32), sums: one zeroed uint64 per contrast entry.  unopose_coloraug_ints(2) = the longest line (crop side) the
+ * blur takes, (3) = the number of opcodes.
+ * _step: chain position `pos` of every crop, src -> dst (src != dst); crops whose chain has ended are copied, crops whose entry is a blur are
+ *     left to _blur_lines.  max_pixels >= every h * w.
+ * _luma_sum: before a _step whose position holds a contrast entry: adds the crop's L values (Pillow's RGB -> L) into its slot of sums.
+ * _blur_lines: Pillow's GaussianBlur as three box passes for the crops whose entry at `pos` is a blur: axis 0 along the rows, src -> dst
+ *     (src != dst), then axis 1 along the columns in place (src == dst).  max_across >= the number of lines / 3, max_line >= their length. */
+int unopose_coloraug_ints(int what);
+int unopose_coloraug_luma_sum(const void *src, int H, int W, const int *desc, const int *ops, int n_crops, int max_pixels, int pos, void *sums,
+                              unopose_stream_t stream);
+int unopose_coloraug_step(const void *src, void *dst, int H, int W, const int *desc, const int *ops, const void *grids, const float *noise,
+                          const void *sums, int n_crops, int max_pixels, int pos, unopose_stream_t stream);
+int unopose_coloraug_blur_lines(const void *src, void *dst, int H, int W, const int *desc, const int *ops, int n_crops, int max_across,
+                                int max_line, int pos, int axis, unopose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,10 @@ SIGNATURES = {
     "unopose_adam_prepare": [_P, _P, _L, _I, _P, _P],
     "unopose_adam_finalise": [_P, _L, _I, _P, _P, _D, _D, _D, _D, _P, _P],
     "unopose_adam_update": [_P, _P, _P, _L, _I, _P, _D, _D, _D, _D, _P],
+    "unopose_coloraug_ints": [_I],
+    "unopose_coloraug_luma_sum": [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P],
+    "unopose_coloraug_step": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "unopose_coloraug_blur_lines": [_P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P],
 }
 
 

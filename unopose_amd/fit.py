@@ -15,6 +15,10 @@
   CPU-only workers).  ``dataset.reset()`` at the start and whenever ``iteration % (max_iter // resample_times) == 0``, as the reference.  Rank r of
   W reads positions r, r + W, ... of ONE endless stream of seeded permutations (:class:`RankSampler`, TrainingSampler's rule).  Worker w of a
   rank seeds ``random``, ``np.random`` and torch with base + w, base = seed + rank * workers.
+* ``--device-crops`` (or ``dataloader.train.device_crops=true``): the workers stop at the window crop and draw the colour augmentation's
+  parameters only (``ColorAugmentor.plan``); ``collate_pairs_device`` ships the crops as one uint8 atlas and ``ops.finish_crops`` runs the
+  augmentation, the mask, the resize and the normalisation on the rank's GPU when the batch is taken.  Same samples as the host route but for
+  the grayscale operator's last bit (``ColorAugmentor``).  Off by default.
 * ranks: ``--gpus N`` starts N fresh processes before this one touches a GPU (RCCL through ``nccl``; ``gloo`` without GPUs); each runs
   ``freeze_backbone`` + ``wrap_ddp``.
 * rank 0 writes, into the output directory, ``model_{iteration:07d}.pth`` every ``period`` iterations (the newest ``max_to_keep`` are kept),
@@ -87,11 +91,17 @@ class _WorkerInit:
 
 
 def build_loader(dataset, batch_size, workers=8, seed=1, rank=0, world=1, start_iteration=0, pin_memory=False):
-    """The training loader over `dataset` (already `reset()`), positioned at the batch of `start_iteration`."""
-    from .provider_train import collate_pairs
+    """The training loader over `dataset` (already `reset()`), positioned at the batch of `start_iteration`.  A `device_crops` dataset is
+    collated by `collate_pairs_device`: its batches are finished by `ops.finish_crops` (fit does that when it takes a batch)."""
+    import functools
 
+    from .provider_train import collate_pairs, collate_pairs_device
+
+    collate = collate_pairs
+    if getattr(dataset, "device_crops", False):
+        collate = functools.partial(collate_pairs_device, img_size=dataset.img_size, rgb_mask_flag=dataset.rgb_mask_flag)
     sampler = RankSampler(len(dataset), seed, rank, world, start=start_iteration * batch_size)
-    return torch.utils.data.DataLoader(dataset, batch_size=batch_size, sampler=sampler, num_workers=workers, collate_fn=collate_pairs,
+    return torch.utils.data.DataLoader(dataset, batch_size=batch_size, sampler=sampler, num_workers=workers, collate_fn=collate,
                                        pin_memory=pin_memory, drop_last=True, worker_init_fn=_WorkerInit(seed + rank * max(workers, 1)),
                                        multiprocessing_context="spawn" if workers else None)
 
@@ -205,7 +215,13 @@ def fit(model, dataset, loader, optimizer, scheduler, output_dir, max_iter, *, p
                 dataset.reset()
                 batches = _batches(loader, iteration)
             t0 = time.perf_counter()
-            batch = {k: v.to(dev, non_blocking=True) for k, v in next(batches).items()}
+            batch = next(batches)
+            if "crop_atlas" in batch:  # a device_crops loader: the colour augmentation, mask, resize and normalisation happen here
+                from .ops import finish_crops
+
+                batch = finish_crops(batch, dev)
+            else:
+                batch = {k: v.to(dev, non_blocking=True) for k, v in batch.items()}
             data_s += time.perf_counter() - t0
             lr = optimizer.param_groups[0]["lr"]
             try:
@@ -263,7 +279,8 @@ def run_settings(cfg, args, world=1):
                 clip_max_norm=float(clip.get("params", {}).get("max_norm", 35)) if clip.get("enabled", False) else None,
                 amp=amp, seed=int(args.seed if args.seed is not None else tr.get("seed", 1)), log_period=int(tr.get("log_period", 50)),
                 batch_size=int(batch), workers=int(workers), output_dir=args.output_dir or cfg.get("misc", {}).get("output_dir"),
-                load_from=args.load_from or cfg.get("misc", {}).get("load_from") or None)
+                load_from=args.load_from or cfg.get("misc", {}).get("load_from") or None,
+                device_crops=bool(args.device_crops or dl.get("device_crops", False)))
 
 
 def _parser():
@@ -278,6 +295,8 @@ def _parser():
     ap.add_argument("--max-procs", type=int, default=16, help="ranks x (workers + 1) is held to this many processes by lowering the workers")
     ap.add_argument("--gpus", type=int, default=1, help="ranks; 0 = one rank on the CPU")
     ap.add_argument("--seed", type=int)
+    ap.add_argument("--device-crops", action="store_true",
+                    help="finish the crops of a batch on the GPU (colour augmentation, mask, resize, normalise); also dataloader.train.device_crops=true")
     ap.add_argument("--print-plan", action="store_true", help="resolve the settings, print them as JSON and stop (touches no GPU)")
     ap.add_argument("opts", nargs="*", help="key=value overrides")
     return ap
@@ -324,7 +343,10 @@ def main(argv=None):
     sched_kw = {k: lm[k] for k in ("warmup_iters", "warmup_factor", "anneal_point", "target_lr_factor") if k in lm}
     scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lambda it: flat_and_anneal_factor(it, s["max_iter"], **sched_kw))
     dc = cfg["dataloader"]["train"]["dataset"]
-    dataset = MegaPoseOneRefTrainSet(dc.get("cfg", dc), num_img_per_epoch=int(dc.get("num_img_per_epoch", -1)), seed=s["seed"] + rank)
+    if s["device_crops"] and not on_gpu:
+        raise SystemExit("--device-crops needs a GPU rank (--gpus >= 1)")
+    dataset = MegaPoseOneRefTrainSet(dc.get("cfg", dc), num_img_per_epoch=int(dc.get("num_img_per_epoch", -1)), seed=s["seed"] + rank,
+                                     device_crops=s["device_crops"])
 
     def loader(iteration):
         return build_loader(dataset, s["batch_size"], s["workers"], s["seed"], rank, world, start_iteration=iteration, pin_memory=on_gpu)

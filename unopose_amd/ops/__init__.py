@@ -5,6 +5,7 @@
     sampling   pixel sampling and the sparse up-projection
     pose       similarity, assignment, coarse / fine pose heads
     prep       query-side instance preparation of the BOP test provider (crops, clouds, pixel indices)
+    augment    the training provider's colour augmentation for all crops of a batch, and the finishing of those crops behind it
     rle        COCO run-length masks: decode (with the depth restriction, count and extents), window crops, encode
     score      pose errors of the BOP'19 scorer (VSD counts, MSSD / MSPD) for many (estimate, ground truth) pairs per launch
     vis        per-image composition of the pose visualisation (nearest-pose layer, boxes, blend, depth-difference image)
@@ -48,6 +49,7 @@ from .pose import (  # noqa: F401
 from .prep import (  # noqa: F401
     PrepPlan, _desc_ints, _tap_table, prep_norm_table, _require, _result, prep_crop_resize, prep_lift, prep_gather,
 )
+from .augment import AugTables, color_augment, finish_crops  # noqa: F401
 from .rle import pack_segs, rle_decode, rle_encode, window_masks  # noqa: F401
 from .score import vsd_counts, pose_errors, pose_metrics, adi, gt_visibility, pts_extent, ref_select  # noqa: F401
 from .vis import compose_poses  # noqa: F401

@@ -67,9 +67,114 @@ def random_rotation_xyz():
     return rx @ ry @ rz
 
 
+# ---- the colour augmentation as "draw" and "apply" -----------------------------------------------------------------------------------
+# Opcodes of an AugPlan entry; csrc/coloraug.hip reads the same numbers (ops/augment.py packs them).
+OP_COARSE_DROPOUT, OP_GAUSSIAN_BLUR, OP_SHARPNESS, OP_CONTRAST, OP_BRIGHTNESS, OP_COLOR, OP_ADD = 0, 1, 2, 3, 4, 5, 6
+OP_INVERT, OP_MULTIPLY_PC, OP_MULTIPLY, OP_GAUSSIAN_NOISE, OP_LINEAR_CONTRAST, OP_GRAYSCALE = 7, 8, 9, 10, 11, 12
+OP_NAMES = ("coarse_dropout", "gaussian_blur", "sharpness", "contrast", "brightness", "color", "add", "invert", "multiply_pc", "multiply",
+            "gaussian_noise", "linear_contrast", "grayscale")
+BLUR_MIN_SIGMA = 1e-3
+
+
+class AugPlan:
+    """What :meth:`ColorAugmentor.plan` drew for one h x w x 3 image: `ops`, an ordered list of (opcode, params).  params: a float32 scalar
+    (blur sigma, the four enhancement factors, grayscale alpha), 3 float32 (add, multiply_pc, multiply, linear_contrast: per channel, a
+    shared draw repeated; invert: 1 = flip), the uint8 ch x cw drop grid (1 = drop), or the float32 h x w x 3 noise field."""
+
+    def __init__(self, h=0, w=0, ops=()):
+        self.h, self.w, self.ops = int(h), int(w), list(ops)
+
+    def __len__(self):
+        return len(self.ops)
+
+
+def image_to_l(img):
+    """Pillow's RGB -> L: (19595 R + 38470 G + 7471 B + 0x8000) >> 16."""
+    a = img.astype(np.uint32)
+    return ((a[..., 0] * 19595 + a[..., 1] * 38470 + a[..., 2] * 7471 + 0x8000) >> 16).astype(np.uint8)
+
+
+def image_blend(deg, img, f):
+    """Pillow's Image.blend(deg, img, f) on uint8 arrays with an fp32 factor: t = deg + f (img - deg) in fp32, truncated; clamped to
+    0 .. 255 first when f is outside [0, 1]."""
+    f = np.float32(f)
+    d = deg.astype(np.float32)
+    t = d + f * (img.astype(np.float32) - d)
+    if not 0 <= f <= 1:
+        t = np.clip(t, np.float32(0), np.float32(255))
+    return t.astype(np.uint8)
+
+
+SMOOTH_KERNEL = np.array([1, 1, 1, 1, 5, 1, 1, 1, 1], np.float32).reshape(3, 3) / np.float32(13)
+
+
+def image_smooth(img):
+    """Pillow's ImageFilter.SMOOTH ([1 1 1; 1 5 1; 1 1 1] / 13): the border ring is copied (so is an image with a side below 3); inside,
+    clamp(floor(0.5 + sum p k)) with the nine products added to 0.5 in row-major order, fp32."""
+    out = img.copy()
+    h, w = img.shape[:2]
+    if h < 3 or w < 3:
+        return out
+    a = img.astype(np.float32)
+    s = np.full((h - 2, w - 2) + img.shape[2:], 0.5, np.float32)
+    for dy in range(3):
+        for dx in range(3):
+            s = s + a[dy:dy + h - 2, dx:dx + w - 2] * SMOOTH_KERNEL[dy, dx]
+    out[1:-1, 1:-1] = np.clip(np.floor(s), 0, 255).astype(np.uint8)
+    return out
+
+
+def box_blur_weights(sigma, passes=3):
+    """Pillow's GaussianBlur(sigma) as `passes` box blurs per axis -> (r, ww, fw): the whole radius, the 8.24 fixed-point weight of a pixel
+    inside it and of the two pixels just outside.  fp32, as BoxBlur.c computes it (the square root and the floor in double, rounded once)."""
+    f = np.float32
+    s2 = f(sigma) * f(sigma) / f(passes)
+    L = f(np.sqrt(12.0 * float(s2) + 1.0))
+    l = f(np.floor((float(L) - 1.0) / 2.0))
+    a = (f(2) * l + f(1)) * (l * (l + f(1)) - f(3) * s2)
+    a = a / (f(6) * (s2 - (l + f(1)) * (l + f(1))))
+    fr = l + a
+    r = int(fr)
+    ww = int(np.uint32(f(1 << 24) / (fr * f(2) + f(1))))
+    fw = (((1 << 24) - (2 * r + 1) * ww) & 0xFFFFFFFF) // 2
+    return r, ww, fw
+
+
+def _box_line(a, r, ww, fw):
+    """One box-blur pass along the last axis of a uint8 array, indices clamped to the line, uint32 wrap-around arithmetic."""
+    n = a.shape[-1]
+    idx = np.arange(n)
+    a32 = a.astype(np.uint32)
+    acc = np.zeros(a.shape, np.uint32)
+    for k in range(-r, r + 1):
+        acc += a32[..., np.clip(idx + k, 0, n - 1)]
+    far = a32[..., np.clip(idx - r - 1, 0, n - 1)] + a32[..., np.clip(idx + r + 1, 0, n - 1)]
+    return ((acc * np.uint32(ww) + far * np.uint32(fw) + np.uint32(1 << 23)) >> np.uint32(24)).astype(np.uint8)
+
+
+def image_gaussian_blur(img, sigma, passes=3):
+    """Pillow's ImageFilter.GaussianBlur(sigma) on an H x W x C uint8 array: three box passes along the rows, then three along the columns,
+    each stored as bytes.  Left alone below BLUR_MIN_SIGMA (ColorAugmentor.gaussian_blur's rule)."""
+    if sigma < BLUR_MIN_SIGMA:
+        return img
+    r, ww, fw = box_blur_weights(sigma, passes)
+    x = np.moveaxis(img, 2, 0)  # C, H, W: lines = rows
+    for _ in range(passes):
+        x = _box_line(x, r, ww, fw)
+    x = np.swapaxes(x, 1, 2)  # C, W, H: lines = columns
+    for _ in range(passes):
+        x = _box_line(x, r, ww, fw)
+    return np.ascontiguousarray(np.moveaxis(np.swapaxes(x, 1, 2), 0, 2))
+
+
 class ColorAugmentor:
     """The reference's colour augmentation (pfoneref_training_dataset_v2.py:158-176; "gdrnpp aug"): thirteen `Sometimes(p, op)`
-    applied in a random order per image.  uint8 HxWx3 in, uint8 out.  Own random generator (see the module docstring)."""
+    applied in a random order per image.  uint8 HxWx3 in, uint8 out.  Own random generator (see the module docstring).
+
+    Two forms: `augment_image` draws and applies in one go (Pillow for the enhancements and the blur); `plan` draws only, consuming the
+    generator exactly as `augment_image` would, and `apply` executes a plan in pure numpy.  `apply` is the specification of the device
+    route (ops.color_augment) and equals `augment_image` but for grayscale, whose luma it adds elementwise ((R 0.299f + G 0.587f) +
+    B 0.114f) where `augment_image` goes through a BLAS product: at most one level apart."""
 
     def __init__(self, seed=None):
         self.rng = np.random.default_rng(seed)
@@ -152,6 +257,117 @@ class ColorAugmentor:
         g = img.astype(np.float32) @ np.array([0.299, 0.587, 0.114], np.float32)
         return self._u8((1 - alpha) * img.astype(np.float32) + alpha * g[:, :, None])
 
+    # -- draw: one method per operator, the same generator calls in the same order as the operator above
+    def _plan_channels(self, p, draw):
+        v = draw(3) if self.rng.random() < p else np.repeat(draw(1), 3)
+        return v.astype(np.float32)
+
+    def _plan_coarse_dropout(self, h, w):
+        ch, cw = max(3, int(round(h * 0.05))), max(3, int(round(w * 0.05)))
+        return (self.rng.random((ch, cw)) < 0.2).astype(np.uint8)
+
+    def _plan_gaussian_blur(self, h, w):
+        sigma = float(self.rng.uniform(0.0, 3.0))
+        return None if sigma < BLUR_MIN_SIGMA else np.float32(sigma)  # None: drawn, but the operator leaves the image alone
+
+    def _plan_sharpness(self, h, w):
+        return np.float32(float(self.rng.uniform(0.0, 50.0)))
+
+    def _plan_contrast(self, h, w):
+        return np.float32(float(self.rng.uniform(0.2, 50.0)))
+
+    def _plan_brightness(self, h, w):
+        return np.float32(float(self.rng.uniform(0.1, 6.0)))
+
+    def _plan_color(self, h, w):
+        return np.float32(float(self.rng.uniform(0.0, 20.0)))
+
+    def _plan_add(self, h, w):
+        return self._plan_channels(0.3, lambda n: self.rng.integers(-25, 26, n))
+
+    def _plan_invert(self, h, w):
+        return (self.rng.random(3) < 0.2).astype(np.float32)
+
+    def _plan_multiply_pc(self, h, w):
+        return self._plan_channels(0.5, lambda n: self.rng.uniform(0.6, 1.4, n))
+
+    def _plan_multiply(self, h, w):
+        return np.repeat(np.float32(self.rng.uniform(0.6, 1.4)), 3)
+
+    def _plan_gaussian_noise(self, h, w):
+        return self.rng.normal(0.0, 10.0, (h, w, 3)).astype(np.float32)
+
+    def _plan_linear_contrast(self, h, w):
+        return self._plan_channels(0.3, lambda n: self.rng.uniform(0.5, 2.2, n))
+
+    def _plan_grayscale(self, h, w):
+        return np.float32(self.rng.uniform(0.0, 1.0))
+
+    def plan(self, h, w):
+        """The draws of `augment_image` for an h x w x 3 image, without the image: the permutation, the coins, every chosen operator's
+        parameters, the drop grid and the noise field.  Leaves `self.rng` where `augment_image` would."""
+        h, w = int(h), int(w)
+        ops = []
+        if h * w == 0:
+            return AugPlan(h, w)
+        for i in self.rng.permutation(len(self.ops)):
+            p, op = self.ops[i]
+            if self.rng.random() < p:
+                name = op.__name__
+                params = getattr(self, "_plan_" + name)(h, w)
+                if params is not None:
+                    ops.append((OP_NAMES.index(name), params))
+        return AugPlan(h, w, ops)
+
+    @staticmethod
+    def apply_op(img, opcode, params):
+        """One plan entry on a uint8 H x W x 3 image, in numpy: integer and fp32 arithmetic exactly as the device kernels do it."""
+        u8 = ColorAugmentor._u8
+        x = img.astype(np.float32)
+        if opcode == OP_COARSE_DROPOUT:
+            h, w = img.shape[:2]
+            ch, cw = params.shape
+            yy = np.minimum((np.arange(h) * ch) // max(h, 1), ch - 1)
+            xx = np.minimum((np.arange(w) * cw) // max(w, 1), cw - 1)
+            return img * (params[yy][:, xx] == 0)[:, :, None].astype(np.uint8)
+        if opcode == OP_GAUSSIAN_BLUR:
+            return image_gaussian_blur(img, params)
+        if opcode == OP_SHARPNESS:
+            return image_blend(image_smooth(img), img, params)
+        if opcode == OP_CONTRAST:
+            lum = image_to_l(img)
+            n = lum.size
+            m = (2 * int(lum.sum(dtype=np.int64)) + n) // (2 * n)  # int(mean + 0.5)
+            return image_blend(np.full_like(img, m), img, params)
+        if opcode == OP_BRIGHTNESS:
+            return image_blend(np.zeros_like(img), img, params)
+        if opcode == OP_COLOR:
+            return image_blend(np.repeat(image_to_l(img)[:, :, None], 3, axis=2), img, params)
+        if opcode in (OP_ADD, OP_GAUSSIAN_NOISE):
+            return u8(x + (params if opcode == OP_GAUSSIAN_NOISE else params.reshape(1, 1, 3)))
+        if opcode == OP_INVERT:
+            return np.where(params.reshape(1, 1, 3) != 0, 255 - img, img).astype(np.uint8)
+        if opcode in (OP_MULTIPLY_PC, OP_MULTIPLY):
+            return u8(x * params.reshape(1, 1, 3))
+        if opcode == OP_LINEAR_CONTRAST:
+            return u8(np.float32(128.0) + params.reshape(1, 1, 3) * (x - np.float32(128.0)))
+        if opcode == OP_GRAYSCALE:
+            alpha = np.float32(params)
+            g = (x[..., 0] * np.float32(0.299) + x[..., 1] * np.float32(0.587)) + x[..., 2] * np.float32(0.114)
+            return u8((np.float32(1) - alpha) * x + alpha * g[:, :, None])
+        raise ValueError(f"ColorAugmentor.apply: opcode {opcode}")
+
+    def apply(self, img, plan):
+        """`plan` on `img` (uint8 H x W x 3) -> uint8.  Pure numpy, no Pillow, no generator."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        if img.size == 0 or len(plan) == 0:
+            return img
+        if img.shape != (plan.h, plan.w, 3):
+            raise ValueError(f"ColorAugmentor.apply: image {img.shape} for a plan over {plan.h} x {plan.w}")
+        for opcode, params in plan.ops:
+            img = np.ascontiguousarray(self.apply_op(img, opcode, params))
+        return img
+
 
 class ViewFiles:
     """The six files of one MegaPose view ``<root>/<subset>/<shard:06d>/<key>.*``, each parsed at most once."""
@@ -203,10 +419,16 @@ class MegaPoseOneRefTrainSet:
     """cfg: data_dir, img_size, n_sample_observed_point, n_sample_model_point, n_sample_template_point, min_px_count_visib,
     min_visib_fract, dilate_mask, rgb_mask_flag, shift_range, optional rgb_to_bgr (attribute or key access).
     ``color_augmentor``: "default" -> :class:`ColorAugmentor`; None -> identity; or any object with ``augment_image``.
-    Usage as the reference's (build_data_loader.py): ``ds.reset()`` once per epoch, then ``ds[i]`` for i < len(ds)."""
+    Usage as the reference's (build_data_loader.py): ``ds.reset()`` once per epoch, then ``ds[i]`` for i < len(ds).
+    ``device_crops=True``: an item carries, in place of ``rgb`` and ``tem1_rgb``, the unfinished crop of each image -- ``rgb_crop`` (uint8
+    window crop, after the BGR option), ``rgb_cropmask`` (uint8 0 / 1), ``rgb_plan`` (the :class:`AugPlan` drawn for it; empty where the
+    0.8 coin failed or there is no augmentor) and the ``tem1_*`` equivalents -- for :func:`collate_pairs_device` and ``ops.finish_crops``.
+    Every draw from ``np.random`` and from the augmentor's generator happens at the same point on both routes; the augmentor must have
+    ``plan``."""
 
-    def __init__(self, cfg, num_img_per_epoch=-1, color_augmentor="default", seed=None):
+    def __init__(self, cfg, num_img_per_epoch=-1, color_augmentor="default", seed=None, device_crops=False):
         get = (lambda k, *d: cfg.get(k, *d)) if hasattr(cfg, "get") else (lambda k, *d: getattr(cfg, k, *d))
+        self.device_crops = bool(device_crops)
         self.data_dir = get("data_dir")
         self.num_img_per_epoch = num_img_per_epoch
         self.dilate_mask, self.rgb_mask_flag = get("dilate_mask"), get("rgb_mask_flag")
@@ -247,6 +469,11 @@ class MegaPoseOneRefTrainSet:
         """colour -> window -> (80 %: colour augmentation) -> foreground only -> resize -> ImageNet-normalised CHW."""
         rgb = files.colour()
         rgb = win.crop(rgb[..., ::-1] if self.bgr else rgb)
+        if self.device_crops:  # the same coin and generator draws; the pixels are left to ops.finish_crops
+            plan = AugPlan()
+            if np.random.rand() < 0.8 and self.color_augmentor is not None:
+                plan = self.color_augmentor.plan(rgb.shape[0], rgb.shape[1])
+            return np.ascontiguousarray(rgb, dtype=np.uint8), np.ascontiguousarray(mask > 0).view(np.uint8), plan
         if np.random.rand() < 0.8 and self.color_augmentor is not None:
             rgb = self.color_augmentor.augment_image(rgb)
         if self.rgb_mask_flag:
@@ -326,12 +553,109 @@ class MegaPoseOneRefTrainSet:
         shift = np.random.uniform(-self.shift_range, self.shift_range, (1, 3))
         target_t = target[:3, 3] + shift[0]
         pts = np.add(pts, shift + 0.001 * np.random.randn(pts.shape[0], 3))
-        return {"pts": torch.FloatTensor(pts), "rgb": torch.FloatTensor(rgb), "rgb_choose": torch.IntTensor(rgb_choose).long(),
+        item = {"pts": torch.FloatTensor(pts), "rgb": None, "rgb_choose": torch.IntTensor(rgb_choose).long(),
                 "translation_label": torch.FloatTensor(target_t), "rotation_label": torch.FloatTensor(target[:3, :3]),
-                "tem1_rgb": torch.FloatTensor(tem_rgb), "tem1_choose": torch.IntTensor(tem_choose).long(),
+                "tem1_rgb": None, "tem1_choose": torch.IntTensor(tem_choose).long(),
                 "tem1_pts": torch.FloatTensor(tem_pts), "K": torch.FloatTensor(K)}
+        for key, stem, image in (("rgb", "rgb_", rgb), ("tem1_rgb", "tem1_", tem_rgb)):
+            if self.device_crops:  # (uint8 crop, uint8 crop mask, AugPlan) in place of the finished tensor
+                del item[key]
+                item.update(zip((stem + "crop", stem + "cropmask", stem + "plan"), image))
+            else:
+                item[key] = torch.FloatTensor(image)
+        return item
 
 
 def collate_pairs(items):
     """Default collation of the training loader: stack every key (all items have the same shapes)."""
     return {k: torch.stack([it[k] for it in items]) for k in items[0]}
+
+
+# ---- the device route: crops, masks and plans travel to the training process, ops.finish_crops finishes them there -------------------
+AUG_DESC_INTS, AUG_ENTRY_INTS = 8, 4  # csrc/coloraug.hip's CAUG_DESC / CAUG_ENTRY (ops.color_augment checks they agree)
+CROP_KEYS = ("crop_atlas", "crop_desc", "crop_ops", "crop_grids", "crop_noise", "crop_masks", "crop_rows", "crop_cfg")
+
+
+def _bits(values):
+    return np.asarray(values, dtype=np.float32).reshape(-1).view(np.int32)
+
+
+def pack_plans(boxes, plans):
+    """The tables csrc/coloraug.hip reads, on the host: boxes = one (y0, h, w) per crop (its rows in the atlas), plans = one AugPlan (or
+    None = empty) per crop -> (desc (n, 8) int32, ops (entries, 4) int32, grids uint8, noise float32), laid out as the kernel file
+    documents.  Never empty arrays: unused tables hold one element."""
+    desc = np.zeros((len(boxes), AUG_DESC_INTS), np.int64)
+    entries, grids, noise = [], [], []
+    n_grid = n_noise = n_sums = 0
+    for c, ((y0, h, w), plan) in enumerate(zip(boxes, plans)):
+        ops = [] if plan is None else plan.ops
+        if ops and (plan.h, plan.w) != (h, w):
+            raise ValueError(f"pack_plans: a plan over {plan.h} x {plan.w} for a {h} x {w} crop")
+        desc[c, :7] = (y0, h, w, len(ops), len(entries), n_grid, n_noise)
+        g_rel = z_rel = 0
+        for opcode, params in ops:
+            e = np.zeros(AUG_ENTRY_INTS, np.int32)
+            e[0] = opcode
+            if opcode == OP_COARSE_DROPOUT:
+                grid = np.ascontiguousarray(params, dtype=np.uint8)
+                e[1:4] = (grid.shape[0], grid.shape[1], g_rel)
+                grids.append(grid.reshape(-1))
+                g_rel += grid.size
+            elif opcode == OP_GAUSSIAN_BLUR:
+                r, ww, fw = box_blur_weights(params)
+                e[1:4] = np.array([r, ww, fw], np.uint32).view(np.int32)
+            elif opcode == OP_GAUSSIAN_NOISE:
+                field = np.ascontiguousarray(params, dtype=np.float32)
+                if field.shape != (h, w, 3):
+                    raise ValueError(f"pack_plans: noise {field.shape} for a {h} x {w} crop")
+                e[1] = z_rel
+                noise.append(field.reshape(-1))
+                z_rel += field.size
+            elif opcode == OP_CONTRAST:
+                e[1], e[2] = _bits(params)[0], n_sums
+                n_sums += 1
+            elif opcode in (OP_SHARPNESS, OP_BRIGHTNESS, OP_COLOR, OP_GRAYSCALE):
+                e[1] = _bits(params)[0]
+            elif opcode in (OP_ADD, OP_INVERT, OP_MULTIPLY_PC, OP_MULTIPLY, OP_LINEAR_CONTRAST):
+                e[1:4] = _bits(params)
+            else:
+                raise ValueError(f"pack_plans: opcode {opcode}")
+            entries.append(e)
+        n_grid, n_noise = n_grid + g_rel, n_noise + z_rel
+    if max(n_noise, n_grid, int(desc.max(initial=0))) >= 2 ** 31:
+        raise ValueError("pack_plans: too many values for 32-bit offsets")
+    return (desc.astype(np.int32), np.stack(entries) if entries else np.zeros((1, AUG_ENTRY_INTS), np.int32),
+            np.concatenate(grids) if grids else np.zeros(1, np.uint8), np.concatenate(noise) if noise else np.zeros(1, np.float32))
+
+
+def build_atlas(crops):
+    """uint8 h x w x 3 crops one under the other -> (atlas (sum h, max w, 3) uint8, rows right of a crop's width zero; boxes (y0, h, w))."""
+    boxes, y = [], 0
+    for c in crops:
+        boxes.append((y, c.shape[0], c.shape[1]))
+        y += c.shape[0]
+    atlas = np.zeros((y, max(c.shape[1] for c in crops), 3), np.uint8)
+    for (y0, h, w), c in zip(boxes, crops):
+        atlas[y0:y0 + h, :w] = c
+    return atlas, boxes
+
+
+def collate_pairs_device(items, img_size, rgb_mask_flag=True):
+    """Collation of `device_crops=True` items: the B query crops, then the B reference crops, in one atlas with their descriptors, plan
+    tables, packed window masks and per-row mask counts (what `ops.finish_crops` uploads and finishes); every other key stacked."""
+    images = [(it[p + "_crop"], it[p + "_cropmask"], it[p + "_plan"]) for p in ("rgb", "tem1") for it in items]
+    crops = [np.asarray(im[0]) for im in images]
+    atlas, boxes = build_atlas(crops)
+    desc, ops, grids, noise = pack_plans(boxes, [im[2] for im in images])
+    masks = [np.ascontiguousarray(np.asarray(im[1]) != 0) for im in images]
+    for m, (_, h, w) in zip(masks, boxes):
+        if m.shape != (h, w):
+            raise ValueError(f"collate_pairs_device: mask {m.shape} for a {h} x {w} crop")
+    skip = {f"{p}_{s}" for p in ("rgb", "tem1") for s in ("crop", "cropmask", "plan")}
+    batch = {k: torch.stack([it[k] for it in items]) for k in items[0] if k not in skip}
+    batch.update(crop_atlas=torch.from_numpy(atlas), crop_desc=torch.from_numpy(desc), crop_ops=torch.from_numpy(ops),
+                 crop_grids=torch.from_numpy(grids), crop_noise=torch.from_numpy(noise),
+                 crop_masks=torch.from_numpy(np.concatenate([m.reshape(-1) for m in masks]).view(np.uint8)),
+                 crop_rows=torch.from_numpy(np.concatenate([m.sum(axis=1, dtype=np.int64) for m in masks]).astype(np.int32)),
+                 crop_cfg=torch.tensor([int(img_size), int(bool(rgb_mask_flag))], dtype=torch.int32))
+    return batch
