@@ -514,6 +514,25 @@ int unopose_render_color(const float *verts, int V, const int *faces, int F, con
                          float ambient, const float *Rt, const float *K4, int P, int H, int W, void *keys, float *depth, void *rgb,
                          unopose_stream_t stream);
 
+/* Shaded, optionally textured and supersampled colour renders of ONE object model in P views (csrc/raster_shade.hip; the images of the
+ * toolkit's scripts/render_train_imgs.py: an OpenGL Phong render at ssaa x the resolution, shrunk by cv2's INTER_AREA).  verts, faces, Rt, K4
+ * as for unopose_render_depth, K4 at the OUTPUT resolution.  Visibility is unopose_render_color's key pass on the (ssaa H, ssaa W) sample grid
+ * with every intrinsic times ssaa (float32): keys is a workspace of P * ssaa^2 * H * W 64-bit words of device memory, 8-byte aligned.
+ * A covered sample, with a_i the perspective-correct weights of the winning face's vertices:
+ *   phong != 0: N = normalize(sum a_i normalize(R n_i)), L = normalize(sum a_i normalize(-P_i)), P_i the camera-space vertex (light at the
+ *               camera), w = min(1, ambient + max(0, N . L)); normalize(0) = 0.  normals (V,3) float32, need not be unit length.
+ *   phong == 0: unopose_render_color's flat weight; normals may be NULL.
+ *   c = the texel at the interpolated uv when texture is given -- texture (Ht,Wt,3) float32 in [0,1], row 0 the TOP row of the image file, uv
+ *       (V,2) float32, v = 0 the bottom row: column min(max(floor(u Wt), 0), Wt - 1), row Ht - 1 - min(max(floor(v Ht), 0), Ht - 1) (nearest,
+ *       clamp to edge) --, else the interpolated colors (V,3) float32 in [0,1] when given, else (surf_r, surf_g, surf_b).  Not both.
+ *   sample byte = (int)(clamp(w c, 0, 1) 255 + 0.5); an uncovered sample is 0.
+ * rgb (P,H,W,3) uint8 = rint((float)(sum of the pixel's ssaa^2 sample bytes) * (1.f / ssaa^2)), ties to even.  ssaa 1 .. 4, ssaa^2 H W <= 2^30.
+ * With phong = 0, ssaa = 1 and no texture rgb equals unopose_render_color's byte for byte.  All float32, no contraction;
+ * unopose_amd/shade_host.py is the same arithmetic in numpy. */
+int unopose_render_shaded(const float *verts, int V, const int *faces, int F, const float *normals, const float *colors, const float *uv,
+                          const float *texture, int Ht, int Wt, float surf_r, float surf_g, float surf_b, float ambient, int phong, int ssaa,
+                          const float *Rt, const float *K4, int P, int H, int W, void *keys, void *rgb, unopose_stream_t stream);
+
 /* One image of the pose visualisation from the renders of its P poses (csrc/vis.hip; visualization.py:93-235 `vis_object_poses`, every cast
  * and evaluation order kept).  rgbs (P,H,W,3) uint8 and depths (P,H,W) float32 in pose order, photo (H,W,3) uint8.
  * _vis_compose: boxes (P,4) int32 = min x, min y, max x, max y of the pixels of a pose with any colour channel > 0 (INT_MAX, INT_MAX, INT_MIN,

@@ -109,6 +109,7 @@ SIGNATURES = {
     "unopose_pose_score": [_P, _P, _I, _I, _F, _P, _P],
     "unopose_render_depth": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P],
     "unopose_render_color": [_P, _I, _P, _I, _P, _F, _F, _F, _F, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "unopose_render_shaded": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
     "unopose_vis_workspace_ints": [],
     "unopose_vis_compose": [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P],
     "unopose_vis_depth_diff": [_P, _P, _I, _I, _F, _P, _P, _P, _P],

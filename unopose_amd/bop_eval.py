@@ -810,16 +810,44 @@ def read_ply_colors(path):
     return _read_ply(path, True)
 
 
-def _read_ply(path, with_colors):
+def read_ply_model(path):
+    """`read_ply_colors` plus what a renderer of the model needs: "normals" (V,3) float64 from the vertex properties `nx, ny, nz`,
+    "texture_uv" (V,2) float64 from `texture_u, texture_v` (None without them) and "texture_file", the NAME of the header's
+    `comment TextureFile NAME` line (None without one; the image lies beside the PLY).  Texture coordinates per FACE (a `texcoord` list
+    property of the face element) are an error: a vertex would need one pair per face it belongs to, and nothing here guesses one.
+    A file without normals gets `vertex_normals(pts, faces)`.  That is this project's rule -- the toolkit's renderers refuse to shade
+    such a model smoothly -- and "normals_computed" says which of the two happened."""
+    out = _read_ply(path, True, True)
+    out["normals_computed"] = out["normals"] is None
+    if out["normals_computed"]:
+        out["normals"] = vertex_normals(out["pts"], out["faces"])
+    return out
+
+
+def vertex_normals(pts, faces):
+    """Area-weighted vertex normals (V,3) float64: every face adds the cross product of its edges (its normal times twice its area) to its
+    three vertices, and the sums are brought to unit length.  A vertex that no face with an area touches keeps the zero vector."""
+    pts, faces = np.asarray(pts, np.float64), np.asarray(faces).reshape(-1, 3)
+    n = np.zeros_like(pts)
+    cross = np.cross(pts[faces[:, 1]] - pts[faces[:, 0]], pts[faces[:, 2]] - pts[faces[:, 0]])
+    for k in range(3):
+        np.add.at(n, faces[:, k], cross)
+    length = np.linalg.norm(n, axis=1, keepdims=True)
+    return np.divide(n, length, out=np.zeros_like(n), where=length > 0)
+
+
+def _read_ply(path, with_colors, with_model=False):
     with open(path, "rb") as f:
         data = f.read()
     end = data.find(b"end_header")
     if not data.startswith(b"ply") or end < 0:
         raise ValueError(f"{path}: not a PLY file")
     body = data.find(b"\n", end) + 1
-    fmt, elements = None, []
+    fmt, elements, texture_file = None, [], None
     for line in data[:end].decode("latin-1").splitlines():
         w = line.split()
+        if len(w) >= 3 and w[:2] == ["comment", "TextureFile"]:
+            texture_file = w[-1]
         if not w or w[0] in ("ply", "comment", "obj_info"):
             continue
         if w[0] == "format":
@@ -848,6 +876,9 @@ def _read_ply(path, with_colors):
                 raise ValueError(f"{path}: vertex properties {props}")
             dtype = np.dtype([(p[1], "<" + _PLY_TYPES[p[0]]) for p in props])
         else:
+            if with_model and any(p[0] == "list" and p[3] == "texcoord" for p in props):
+                raise ValueError(f"{path}: texture coordinates per face (the `texcoord` list property) are not read: "
+                                 "save the model with per-vertex `texture_u`, `texture_v`")
             if len(props) != 1 or not lists or props[0][3] not in ("vertex_indices", "vertex_index"):
                 raise ValueError(f"{path}: face properties {props} (one list of vertex indices is read)")
             dtype = np.dtype([("n", "<" + _PLY_TYPES[props[0][1]]), ("v", "<" + _PLY_TYPES[props[0][2]], (3,))])
@@ -873,6 +904,11 @@ def _read_ply(path, with_colors):
                 if {"red", "green", "blue"} <= set(kinds):
                     chans = [np.asarray(rec[k], np.float64) / (np.iinfo(kinds[k]).max if kinds[k].kind in "iu" else 1.0) for k in ("red", "green", "blue")]
                     out["colors"] = np.clip(np.stack(chans, axis=1), 0.0, 1.0)
+            if with_model:
+                names = {p[1] for p in props}
+                for key, wanted in (("normals", ("nx", "ny", "nz")), ("texture_uv", ("texture_u", "texture_v"))):
+                    out[key] = np.stack([np.asarray(rec[k], np.float64) for k in wanted], axis=1) if set(wanted) <= names else None
+                out["texture_file"] = texture_file
         else:
             out["faces"] = np.asarray(rec["v"]).astype(np.int32).reshape(count, 3)
     if "pts" not in out:

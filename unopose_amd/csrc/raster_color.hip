@@ -6,6 +6,7 @@
 //            face wins a pixel and, at equal depth, the face of the lowest index -- whatever order the threads arrive in;
 //   resolve  a thread per (pose, pixel) reads the winner, recomputes its barycentrics with the same expressions and shades the pixel;
 //            the depth written is the key's upper half, so it carries the bits unopose_render_depth writes.
+// The triangle setup, the key pass and the shading expressions live in csrc/raster_keys.h, which csrc/raster_shade.hip shares.
 // Shading is the toolkit's flat shader restated: the face normal n is the cross product of the camera-space
 // edges, the fragment position is Pc = ((x - cx) / fx z, (y - cy) / fy z, z), the light sits at the camera origin and the weight is
 // w = min(1, ambient + |n . Pc| / (|n| |Pc|)); |.| because the toolkit's normal comes from screen derivatives and always faces the viewer.
@@ -14,11 +15,9 @@
 // tests/raster_rgb_np.py is the same arithmetic in numpy float32; the two agree bit for bit.
 #include <algorithm>
 
-#include "common.h"
+#include "raster_keys.h"
 
 namespace unopose {
-
-static constexpr unsigned long long RASTER_EMPTY_KEY = 0x7F800000FFFFFFFFull;  // +inf, no face
 
 __global__ __launch_bounds__(256) void raster_key_fill_kernel(unsigned long long *__restrict__ buf, long n) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) buf[i] = RASTER_EMPTY_KEY;
@@ -29,39 +28,8 @@ __global__ __launch_bounds__(256) void raster_key_kernel(const float *__restrict
                                                         unsigned long long *__restrict__ keys) {
   const int f = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
   if (f >= F) return;
-  const float *R = Rt + (size_t)p * 12, *t = R + 9, *K = K4 + (size_t)p * 4;
-  float X[3], Y[3], Z[3], u[3], v[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float *q = verts + (size_t)faces[f * 3 + i] * 3;
-    X[i] = R[0] * q[0] + R[1] * q[1] + R[2] * q[2] + t[0];
-    Y[i] = R[3] * q[0] + R[4] * q[1] + R[5] * q[2] + t[1];
-    Z[i] = R[6] * q[0] + R[7] * q[1] + R[8] * q[2] + t[2];
-    if (!(Z[i] > 1e-6f)) return;
-    u[i] = K[0] * X[i] / Z[i] + K[2];
-    v[i] = K[1] * Y[i] / Z[i] + K[3];
-  }
-  const float area = (u[1] - u[0]) * (v[2] - v[0]) - (u[2] - u[0]) * (v[1] - v[0]);
-  if (fabsf(area) < 1e-12f) return;
-  const int x0 = max(0, (int)ceilf(fminf(fminf(u[0], u[1]), u[2]))), x1 = min(W - 1, (int)floorf(fmaxf(fmaxf(u[0], u[1]), u[2])));
-  const int y0 = max(0, (int)ceilf(fminf(fminf(v[0], v[1]), v[2]))), y1 = min(H - 1, (int)floorf(fmaxf(fmaxf(v[0], v[1]), v[2])));
-  const float inv = 1.f / area, iz0 = 1.f / Z[0], iz1 = 1.f / Z[1], iz2 = 1.f / Z[2];
-  unsigned long long *kb = keys + (size_t)p * H * W;
-  for (int y = y0; y <= y1; ++y)
-    for (int x = x0; x <= x1; ++x) {
-      const float px = (float)x, py = (float)y;
-      const float b0 = ((u[1] - px) * (v[2] - py) - (u[2] - px) * (v[1] - py)) * inv;
-      const float b1 = ((u[2] - px) * (v[0] - py) - (u[0] - px) * (v[2] - py)) * inv;
-      const float b2 = 1.f - b0 - b1;
-      if (b0 < 0.f || b1 < 0.f || b2 < 0.f) continue;
-      const float z = 1.f / (b0 * iz0 + b1 * iz1 + b2 * iz2);
-      if (z > 0.f) atomicMin(kb + (size_t)y * W + x, ((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)(uint32_t)f);
-    }
-}
-
-__device__ __forceinline__ unsigned char shade_byte(float w, float c) {
-  const float s = fminf(fmaxf(w * c, 0.f), 1.f);
-  return (unsigned char)(int)(s * 255.f + 0.5f);
+  const float *R = Rt + (size_t)p * 12, *K = K4 + (size_t)p * 4;
+  raster_face_keys(verts, faces, f, R, R + 9, K[0], K[1], K[2], K[3], H, W, keys + (size_t)p * H * W);  // csrc/raster_keys.h
 }
 
 __global__ __launch_bounds__(256) void raster_resolve_kernel(const float *__restrict__ verts, const int *__restrict__ faces, int F,
@@ -82,40 +50,20 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const float *__rest
     return;
   }
   depth[at] = __uint_as_float(zbits);
-  const float *R = Rt + (size_t)p * 12, *t = R + 9, *K = K4 + (size_t)p * 4;
-  int vi[3];
-  float X[3], Y[3], Z[3], u[3], v[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    vi[k] = faces[(size_t)f * 3 + k];
-    const float *q = verts + (size_t)vi[k] * 3;
-    X[k] = R[0] * q[0] + R[1] * q[1] + R[2] * q[2] + t[0];
-    Y[k] = R[3] * q[0] + R[4] * q[1] + R[5] * q[2] + t[1];
-    Z[k] = R[6] * q[0] + R[7] * q[1] + R[8] * q[2] + t[2];
-    u[k] = K[0] * X[k] / Z[k] + K[2];
-    v[k] = K[1] * Y[k] / Z[k] + K[3];
-  }
-  const float area = (u[1] - u[0]) * (v[2] - v[0]) - (u[2] - u[0]) * (v[1] - v[0]);
-  const float inv = 1.f / area, iz0 = 1.f / Z[0], iz1 = 1.f / Z[1], iz2 = 1.f / Z[2];
+  const float *R = Rt + (size_t)p * 12, *K = K4 + (size_t)p * 4;
+  RasterFace T;
+  raster_face_setup(verts, faces, (size_t)f, R, R + 9, K[0], K[1], K[2], K[3], T);
+  const float inv = 1.f / raster_face_area(T), iz0 = 1.f / T.Z[0], iz1 = 1.f / T.Z[1], iz2 = 1.f / T.Z[2];
   const int y = (int)(i / W), x = (int)(i - (long)y * W);
   const float px = (float)x, py = (float)y;
-  const float b0 = ((u[1] - px) * (v[2] - py) - (u[2] - px) * (v[1] - py)) * inv;
-  const float b1 = ((u[2] - px) * (v[0] - py) - (u[0] - px) * (v[2] - py)) * inv;
-  const float b2 = 1.f - b0 - b1;
+  float b0, b1, b2;
+  raster_barycentrics(T, inv, px, py, b0, b1, b2);
   const float z = 1.f / (b0 * iz0 + b1 * iz1 + b2 * iz2);
-  // flat shading: light at the camera origin, the normal of the face from its camera-space edges
-  const float e1x = X[1] - X[0], e1y = Y[1] - Y[0], e1z = Z[1] - Z[0];
-  const float e2x = X[2] - X[0], e2y = Y[2] - Y[0], e2z = Z[2] - Z[0];
-  const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
-  const float pcx = (px - K[2]) / K[0] * z, pcy = (py - K[3]) / K[1] * z;
-  const float dot = nx * pcx + ny * pcy + nz * z;
-  const float len = sqrtf(nx * nx + ny * ny + nz * nz) * sqrtf(pcx * pcx + pcy * pcy + z * z);
-  const float cosine = len > 0.f ? fabsf(dot) / len : 0.f;
-  const float w = fminf(1.f, ambient + cosine);
+  const float w = raster_flat_weight(T, K[0], K[1], K[2], K[3], px, py, z, ambient);
   float cr = sr, cg = sg, cb = sb;
   if (colors) {  // perspective-correct: colour / z is linear on the screen
     const float w0 = b0 * iz0, w1 = b1 * iz1, w2 = b2 * iz2;
-    const float *c0 = colors + (size_t)vi[0] * 3, *c1 = colors + (size_t)vi[1] * 3, *c2 = colors + (size_t)vi[2] * 3;
+    const float *c0 = colors + (size_t)T.vi[0] * 3, *c1 = colors + (size_t)T.vi[1] * 3, *c2 = colors + (size_t)T.vi[2] * 3;
     cr = (w0 * c0[0] + w1 * c1[0] + w2 * c2[0]) * z;
     cg = (w0 * c0[1] + w1 * c1[1] + w2 * c2[1]) * z;
     cb = (w0 * c0[2] + w1 * c1[2] + w2 * c2[2]) * z;
