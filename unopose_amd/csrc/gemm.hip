@@ -9,15 +9,16 @@
 //     swizzle lives on the per-lane SOURCE address: LDS slot (row, p) holds the row's 16-byte chunk
 //     c = p ^ ((row >> 1) & 7)  and the fragment reads apply the same XOR -- every ds_read_b128 lane group then covers
 //     all 16 slots of the 256-byte bank row (conflict-free), and every DMA instruction still fetches full 128-byte lines;
-//   * 8 waves as 2 (M) x 4 (N), 128 x 64 outputs per wave, v_mfma_f32_32x32x16_bf16 with the operands SWAPPED
-//     (rows of the MFMA result = output columns n): a lane then owns 4 consecutive n of one output row, which
-//     packs to 8-byte LDS writes in the epilogue;
+//   * 8 waves as 2 (M) x 4 (N), 128 x 64 outputs per wave, v_mfma_f32_16x16x32_bf16 (8 x 4 accumulators of 16 x 16 per wave: at the
+//     same tile per wave and cycles per flop the chip holds a higher clock under this shape than under 32 x 32 x 16) with the
+//     operands SWAPPED (rows of the MFMA result = output columns n): a lane then owns 4 consecutive n of one output row, which
+//     packs to 8-byte LDS writes in the epilogue.  The lane -> (row, columns) mapping lives in ONE place, gemm_kernel.h's AccTile;
 //   * ROUND 4 -- the K loop is a HALF-TILE STREAM with COUNTED waits (never vmcnt(0) inside the stream).  A K-tile is four
 //     16-KiB half-tiles in stream order  A0 (rows 0-63 of each wave row-block), B0 (columns 0-31 of each wave column-block),
 //     B1, A1;  the ring is 2 K-tiles x 4 half-tile slots = 128 KiB.  A K-tile is computed in two PHASES of two 64 x 32 output
-//     quadrants over the whole K-step each (16 MFMAs):  X = (A0 x B0, A0 x B1),  Y = (A1 x B1, A1 x B0),  and every phase is
+//     quadrants over the whole K-step each (32 MFMAs):  X = (A0 x B0, A0 x B1),  Y = (A1 x B1, A1 x B0),  and every phase is
 //         [fragment reads of the phase | LDS-DMA pieces (X: one half-tile, Y: three) | s_waitcnt vmcnt(8) | lgkmcnt(0)]
-//         s_barrier   [16 MFMAs]   s_barrier
+//         s_barrier   [32 MFMAs]   s_barrier
 //     Four half-tiles (8 loads per wave) stay in flight ACROSS the barriers; a half-tile is read one phase after the wait
 //     that covers it and its slot is refilled one phase after its last read (reads retired before the barrier).
 //     The two wave groups (wm = 0 / 1: one wave of each per SIMD) run ONE BARRIER apart, so one group's MFMA segment sits

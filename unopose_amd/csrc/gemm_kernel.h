@@ -26,6 +26,34 @@ constexpr int GEMM_ROTX = 5, GEMM_ROTS = 3;
 #define GEMM_LNF_MAXPARTS 4
 #define GEMM_LDS_SHIFT (GEMM_LDS_LNPART + 8192)  // EPI 5: the row shifts of each wave's 128 rows, 512 B per wave (4 KiB)
 
+// The 128 x 64 accumulator tile of a wave as v_mfma_f32_16x16x32_bf16 leaves it with the operands swapped (W fragment first): the tile is
+// NRB blocks of RB rows x NCG blocks of 16 columns, one f32x4 accumulator each; lane L owns row L & 15 of every row block and, of that
+// row, the four consecutive columns 4 (L >> 4) .. + 3 of every column block.  The only place that knows the mapping: the fragment reads
+// of the K loop and every epilogue go through it.  (The shape: at the same tile per wave and the same cycles per flop the chip holds a
+// higher clock under 16 x 16 x 32 than under 32 x 32 x 16 -- bf16 step 28.9 -> 28.1 ms, fp32-class 71.3 -> 68.6 ms)
+struct AccTile {
+  static constexpr int RB = 16;         // rows of a row block (= lanes that hold different rows)
+  static constexpr int NRB = 128 / RB;  // row blocks of the wave's 128 rows
+  static constexpr int NP = 64 / RB;    // lanes that share a row (L, L + 16, L + 32, L + 48: the four lane quarters)
+  static constexpr int NCG = 16 / NP;   // column groups (4 consecutive columns) a lane holds of its row: one per 16-column block
+  static constexpr int NKS = 8 / NP;    // MFMA k-steps of one 128-byte operand line (8 chunks of 16 bytes, NP per step)
+  typedef f32x4 frag;                   // one MFMA accumulator: acc[column group][row block]
+  static __device__ __forceinline__ int row(int lane) { return lane & (RB - 1); }  // row of the lane within a row block
+  // which of the NP sharers of that row (masked: the epilogues pass laundered lane numbers, and the known range folds their slot arithmetic)
+  static __device__ __forceinline__ int part(int lane) { return (lane / RB) & (NP - 1); }
+  // first column (of the wave's 64) of column group cg of a lane of part `pt`
+  static __device__ __forceinline__ int col0(int cg, int pt) { return cg * (4 * NP) + 4 * pt; }
+  static __device__ __forceinline__ f32x4 get(const frag (&acc)[NCG][NRB], int rb, int cg) { return acc[cg][rb]; }
+  static __device__ __forceinline__ void set(frag (&acc)[NCG][NRB], int rb, int cg, f32x4 v) { acc[cg][rb] = v; }
+  // fragment read: byte offset, within a block of RB operand rows (RB * 128 bytes), of the lane's 16-byte chunk of k-step ks:
+  // tile row r, chunk c = NP ks + part at (r >> 3) * 1024 + (r & 7) * 128 + ((c ^ ((r >> 1) & 7)) << 4)
+  static __device__ __forceinline__ uint32_t frag_off(int ks, int lane) {
+    const int r = row(lane), c = NP * ks + part(lane);
+    return (uint32_t)((r >> 3) * 1024 + (r & 7) * 128 + ((c ^ ((r >> 1) & 7)) << 4));
+  }
+  static __device__ __forceinline__ frag mfma(bf16x8 w, bf16x8 a, frag c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, a, c, 0, 0, 0); }
+};
+
 // GATHER (grouped, row-gathered form; unopose_linear_bf16_gather): output row r of tile t is A row row_list[256 t + r]
 // times the 256-row weight block of the group tile t belongs to (tile_info[1 + g] = first tile of group g, g = 0..N/256;
 // tile_info[0] = number of tiles, read on the device: the host never learns it); C is (tiles * 256, 256).
@@ -72,6 +100,8 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
   static_assert(F32 || EPI != 4, "EPI 4 (bf16 + residual out of fp32-class operands) is an F32 epilogue");
   constexpr int ESZ = F32 ? 4 : 2;                        // bytes per k of an operand row
   constexpr int KT = F32 ? 32 : 64;                       // k per K-tile (128-byte rows either way)
+  using T = AccTile;                                      // the accumulator layout (16 x 16 x 32 MFMAs)
+  using frag = T::frag;
   const char *A = reinterpret_cast<const char *>(Av), *W = reinterpret_cast<const char *>(Wv);
   // row strides in elements (0 = dense; unopose_linear_bf16_ld)
   const int LDA = lda ? lda : K, LDW = ldw ? ldw : K, LDC = ldc ? ldc : N;
@@ -85,8 +115,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
   }
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
-  const int l31 = lane & 31, hi = lane >> 5;
-  const int l31_ = l31, hi_ = hi, lane_ = lane;  // (names for the fp32-class epilogue's laundered copies)
+  const int lane_ = lane;  // (name for the epilogues' laundered copies)
   // ---- persistent, lock-stepped tile walk.  The grid is ONE workgroup per CU (gridDim.x <= 256, a multiple of 8;
   // 130 KiB of LDS admits one per CU).  Workgroup b sits on XCD b % 8 (observed dispatch rule: a SPEED assumption
   // only) and is slot b / 8 of that XCD; XCD x owns one contiguous range of the tile sequence and its slots take
@@ -113,14 +142,13 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
   const __amdgpu_buffer_rsrc_t b_rs = __builtin_amdgcn_make_buffer_rsrc((void *)bias, 0, N * 4, 0x00020000);
   const int nk = K / KT;
 
-  // ---- fragment read addresses: tile row r = base + l31 (base a multiple of 32), chunk c = 2 ks + hi:
-  //      byte = (r >> 3) * 1024 + (r & 7) * 128 + ((c ^ ((r >> 1) & 7)) << 4)
-  const int fx = (l31 >> 1) & 7;
-  uint32_t fr_off[4];
+  // ---- fragment read addresses (AccTile::frag_off): blocks of T::RB operand rows are T::RB * 128 bytes apart
+  uint32_t fr_off[T::NKS];
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) fr_off[ks] = (uint32_t)((l31 >> 3) * 1024 + (l31 & 7) * 128 + ((((ks << 1) | hi) ^ fx) << 4));
-  const uint32_t a_base = (uint32_t)(wm * 16384);                // A rows wm*128 ..  (+ ah * 8192 + mbl * 4096)
-  const uint32_t w_base = (uint32_t)(GEMM_OPBYTES + wn * 8192);  // W rows wn*64 ..   (+ bh * 4096)
+  for (int ks = 0; ks < T::NKS; ++ks) fr_off[ks] = T::frag_off(ks, lane);
+  constexpr int ABH = 64 / T::RB, BBH = 32 / T::RB, BLKB = T::RB * GEMM_ROWB;  // row blocks of an A half / a B half; bytes of a block
+  const uint32_t a_base = (uint32_t)(wm * 16384);                // A rows wm*128 ..  (+ ah * 8192 + mbl * BLKB)
+  const uint32_t w_base = (uint32_t)(GEMM_OPBYTES + wn * 8192);  // W rows wn*64 ..   (+ bh * 4096 + nbl * BLKB)
   // ---- LDS-DMA destinations of this wave's two pieces of a half-tile (within a buffer); piece i at + i * 1024
   //      A half ah: rows (wave >> 2) * 128 + ah * 64 + (wave & 3) * 16 + 8 i ..;   B half bh: rows (wave >> 1) * 64 + bh * 32 + (wave & 1) * 16 + 8 i ..
   const uint32_t a_dst = (uint32_t)((wave >> 2) * 16384 + (wave & 3) * 2048);
@@ -285,62 +313,68 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
     // the accumulators start at the bias (EPI 3 adds it in its LayerNorm epilogue): the bias slice landed with an earlier wait of
     // the stream (it is the OLDEST load of a fresh pipeline; in a continuing stream it was issued 6 phases before this point)
     const float *bias_lds = reinterpret_cast<const float *>(smem + GEMM_LDS_BIAS + bsel * 1024);
-    f32x16 acc[2][4];
+    frag acc[T::NCG][T::NRB];
+    {
+      const int pt = T::part(lane);
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb)
+      for (int cg = 0; cg < T::NCG; ++cg) {
+        const float4 bv = EPI == 3 || LNF ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4 *>(bias_lds + wn * 64 + T::col0(cg, pt));
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 bv = EPI == 3 || LNF ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4 *>(bias_lds + wn * 64 + nb * 32 + 8 * g + 4 * hi);
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) {
-          acc[nb][mb][4 * g + 0] = bv.x;
-          acc[nb][mb][4 * g + 1] = bv.y;
-          acc[nb][mb][4 * g + 2] = bv.z;
-          acc[nb][mb][4 * g + 3] = bv.w;
-        }
+        for (int rb = 0; rb < T::NRB; ++rb) T::set(acc, rb, cg, f32x4{bv.x, bv.y, bv.z, bv.w});
       }
+    }
 
-    bf16x8 af[2][4], wf0[4], wf1[4];  // A half (2 row blocks x 4 k-substeps), B0, B1
+    // A half: ABH row blocks x NKS k-steps ([mbl * NKS + ks]); B0, B1: BBH column blocks x NKS k-steps -- 8 + 4 + 4 fragments
+    bf16x8 af[ABH * T::NKS], wf0[BBH * T::NKS], wf1[BBH * T::NKS];
     auto read_a = [&](const char *lb, int ah) {
 #pragma unroll
-      for (int mbl = 0; mbl < 2; ++mbl)
+      for (int mbl = 0; mbl < ABH; ++mbl)
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) af[mbl][ks] = *reinterpret_cast<const bf16x8 *>(lb + a_base + ah * 8192 + mbl * 4096 + fr_off[ks]);
+        for (int ks = 0; ks < T::NKS; ++ks)
+          af[mbl * T::NKS + ks] = *reinterpret_cast<const bf16x8 *>(lb + a_base + ah * 8192 + mbl * BLKB + fr_off[ks]);
     };
-    auto read_b = [&](const char *lb, int bh, bf16x8(&wf)[4]) {
+    auto read_b = [&](const char *lb, int bh, bf16x8(&wf)[BBH * T::NKS]) {
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) wf[ks] = *reinterpret_cast<const bf16x8 *>(lb + w_base + bh * 4096 + fr_off[ks]);
+      for (int nbl = 0; nbl < BBH; ++nbl)
+#pragma unroll
+        for (int ks = 0; ks < T::NKS; ++ks)
+          wf[nbl * T::NKS + ks] = *reinterpret_cast<const bf16x8 *>(lb + w_base + bh * 4096 + nbl * BLKB + fr_off[ks]);
     };
-    // one quadrant: 2 row blocks (ah) x 1 column block (bh) x 4 k-substeps, the two accumulators alternating
-    auto mfma_q = [&](int ah, int bh, const bf16x8(&wf)[4]) {
-      if (F32) {
-        // fragments 0 / 1 = the hi parts of the two 16-k blocks, 2 / 3 = their lo parts; small terms first
+    // one quadrant: an A half (ah) x a B half (bh) x the k-steps of the K-tile; consecutive MFMAs go to different accumulators
+    auto mfma_q = [&](int ah, int bh, const bf16x8(&wf)[BBH * T::NKS]) {
+      if constexpr (F32) {
+        // the split line [hi(32 bf16) | lo(32 bf16)]: k-step 0 = the hi parts of the line's 32 k, k-step 1 = their lo parts;
+        // per accumulator lo.hi, hi.lo, hi.hi -- small terms first
 #pragma unroll
-        for (int b = 0; b < 2; ++b)
+        for (int term = 0; term < 3; ++term)
 #pragma unroll
-          for (int mbl = 0; mbl < 2; ++mbl) {
-            f32x16 &a = acc[bh][2 * ah + mbl];
-            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[2 + b], af[mbl][b], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[b], af[mbl][2 + b], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[b], af[mbl][b], a, 0, 0, 0);
-          }
-        return;
+          for (int nbl = 0; nbl < BBH; ++nbl)
+#pragma unroll
+            for (int mbl = 0; mbl < ABH; ++mbl) {
+              frag &a = acc[bh * BBH + nbl][ah * ABH + mbl];
+              a = T::mfma(wf[nbl * T::NKS + (term == 0 ? 1 : 0)], af[mbl * T::NKS + (term == 1 ? 1 : 0)], a);
+            }
+      } else {
+#pragma unroll
+        for (int ks = 0; ks < T::NKS; ++ks)
+#pragma unroll
+          for (int nbl = 0; nbl < BBH; ++nbl)
+#pragma unroll
+            for (int mbl = 0; mbl < ABH; ++mbl) {
+              frag &a = acc[bh * BBH + nbl][ah * ABH + mbl];
+              a = T::mfma(wf[nbl * T::NKS + ks], af[mbl * T::NKS + ks], a);
+            }
       }
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-        for (int mbl = 0; mbl < 2; ++mbl)
-          acc[bh][2 * ah + mbl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], af[mbl][ks], acc[bh][2 * ah + mbl], 0, 0, 0);
     };
     if (wm == 1) __builtin_amdgcn_s_barrier();  // group 1 runs one barrier behind group 0
-    // ---- K loop: two phases per K-tile, 16 MFMAs each.  X(t) = (A0 x B0, A0 x B1) reads A0, B0, B1 of K-tile t and issues A1 of
+    // ---- K loop: two phases per K-tile, 32 MFMAs of 16 x 16 x 32 each (fp32-class: 48, three per product).  X(t) = (A0 x B0, A0 x B1) reads A0, B0, B1 of K-tile t and issues A1 of
     // K-tile t + 1 (the first X of a tile also B1 of K-tile 1, which the epilogue before it kept out of its staging slot);
     // Y(t) = (A1 x B1, A1 x B0) reads A1 and issues A0, B0, B1 of K-tile t + 2.  Each phase is
-    //     [reads | DMA pieces | vmcnt(8) | lgkmcnt(0)]  s_barrier  [16 MFMAs]  s_barrier
+    //     [reads | DMA pieces | vmcnt(8) | lgkmcnt(0)]  s_barrier  [MFMAs]  s_barrier
     // A slot is refilled ONE phase after its last read, which is why the reads are retired BEFORE the phase's first barrier;
     // a half-tile is read one phase after the wait that covers it.  Every wait leaves 4 half-tiles (8 loads) in flight; near the
     // end of a tile the stream either continues with the NEXT tile's half-tiles (`more`) or ends, the waits counting down 2 / 0.
-    // One loop body (uniform scalar branches around DMA issue and waits only), so the 32 MFMAs accumulate in place.
+    // One loop body (uniform scalar branches around DMA issue and waits only), so the MFMAs accumulate in place.
     auto phase = [&](auto compute) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
@@ -436,63 +470,62 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
     par ^= GEMM_BUFBYTES;                       // back to the LAST K-tile's buffer: its A1 / B1 slots stage C (restored below)
     if (EPI == 3) {
       // v = acc + bias + residual; row statistics across the 4 column waves through LDS; normalise in place
+      const int row = T::row(lane), pt = T::part(lane);
 #pragma unroll
-      for (int mb = 0; mb < 4; ++mb) {
-        const int m = min(m0 + wm * 128 + mb * 32 + l31, M - 1);
-        const u16 *rp = resid + (size_t)m * GEMM_BN + wn * 64 + 4 * hi;
+      for (int rb = 0; rb < T::NRB; ++rb) {
+        const int m = min(m0 + wm * 128 + rb * T::RB + row, M - 1);
+        const u16 *rp = resid + (size_t)m * GEMM_BN + wn * 64;
         float a1 = 0.f, a2 = 0.f;
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
+        for (int cg = 0; cg < T::NCG; ++cg) {
+          const int nl = T::col0(cg, pt);
+          const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias_lds + wn * 64 + nl);
+          const uint2 r = *reinterpret_cast<const uint2 *>(rp + nl);
+          f32x4 v = T::get(acc, rb, cg);
+          v[0] = v[0] + bv[0] + __uint_as_float(r.x << 16);
+          v[1] = v[1] + bv[1] + __uint_as_float(r.x & 0xffff0000u);
+          v[2] = v[2] + bv[2] + __uint_as_float(r.y << 16);
+          v[3] = v[3] + bv[3] + __uint_as_float(r.y & 0xffff0000u);
+          T::set(acc, rb, cg, v);
+          a1 += (v[0] + v[1]) + (v[2] + v[3]);
+          a2 += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+        }
 #pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int nl = nb * 32 + 8 * g + 4 * hi;
-            const float4 bv = *reinterpret_cast<const float4 *>(bias_lds + wn * 64 + nl);
-            const uint2 r = *reinterpret_cast<const uint2 *>(rp + nb * 32 + 8 * g);
-            const float v0 = acc[nb][mb][4 * g + 0] + bv.x + __uint_as_float(r.x << 16);
-            const float v1 = acc[nb][mb][4 * g + 1] + bv.y + __uint_as_float(r.x & 0xffff0000u);
-            const float v2 = acc[nb][mb][4 * g + 2] + bv.z + __uint_as_float(r.y << 16);
-            const float v3 = acc[nb][mb][4 * g + 3] + bv.w + __uint_as_float(r.y & 0xffff0000u);
-            acc[nb][mb][4 * g + 0] = v0;
-            acc[nb][mb][4 * g + 1] = v1;
-            acc[nb][mb][4 * g + 2] = v2;
-            acc[nb][mb][4 * g + 3] = v3;
-            a1 += (v0 + v1) + (v2 + v3);
-            a2 += (v0 * v0 + v1 * v1) + (v2 * v2 + v3 * v3);
-          }
-        a1 += __shfl_xor(a1, 32);  // lanes l31 and l31 + 32 hold complementary columns of the same row
-        a2 += __shfl_xor(a2, 32);
-        if (hi == 0) ln_part[((wm * 4 + mb) * 32 + l31) * 4 + wn] = make_float2(a1, a2);
+        for (int d = T::RB; d < 64; d <<= 1) {  // the NP lanes L, L + RB, ... hold complementary columns of the same row
+          a1 += __shfl_xor(a1, d);
+          a2 += __shfl_xor(a2, d);
+        }
+        if (pt == 0) ln_part[(wm * 128 + rb * T::RB + row) * 4 + wn] = make_float2(a1, a2);
       }
       __syncthreads();
 #pragma unroll
-      for (int mb = 0; mb < 4; ++mb) {
-        const float2 *pp = ln_part + ((wm * 4 + mb) * 32 + l31) * 4;
+      for (int rb = 0; rb < T::NRB; ++rb) {
+        const float2 *pp = ln_part + (wm * 128 + rb * T::RB + row) * 4;
         const float t1 = (pp[0].x + pp[1].x) + (pp[2].x + pp[3].x), t2 = (pp[0].y + pp[1].y) + (pp[2].y + pp[3].y);
         const float mean = t1 * (1.f / GEMM_BN);
         const float rstd = rsqrtf(fmaxf(t2 * (1.f / GEMM_BN) - mean * mean, 0.f) + ln_eps);
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
+        for (int cg = 0; cg < T::NCG; ++cg) {
+          const int nl = wn * 64 + T::col0(cg, pt);
+          const f32x4 gw = *reinterpret_cast<const f32x4 *>(lnw_lds + nl), gb = *reinterpret_cast<const f32x4 *>(lnb_lds + nl);
+          f32x4 v = T::get(acc, rb, cg);
 #pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int nl = wn * 64 + nb * 32 + 8 * g + 4 * hi;
-            const float4 gw = *reinterpret_cast<const float4 *>(lnw_lds + nl), gb = *reinterpret_cast<const float4 *>(lnb_lds + nl);
-            acc[nb][mb][4 * g + 0] = (acc[nb][mb][4 * g + 0] - mean) * rstd * gw.x + gb.x;
-            acc[nb][mb][4 * g + 1] = (acc[nb][mb][4 * g + 1] - mean) * rstd * gw.y + gb.y;
-            acc[nb][mb][4 * g + 2] = (acc[nb][mb][4 * g + 2] - mean) * rstd * gw.z + gb.z;
-            acc[nb][mb][4 * g + 3] = (acc[nb][mb][4 * g + 3] - mean) * rstd * gw.w + gb.w;
-          }
+          for (int e = 0; e < 4; ++e) v[e] = (v[e] - mean) * rstd * gw[e] + gb[e];
+          T::set(acc, rb, cg, v);
+        }
       }
     }
     if constexpr (LNF) {
       // ---- LayerNorm applied algebraically on the accumulators: out = rstd_r * acc - (rstd_r * mean_r) * c_n + d_n
-      int l31 = l31_, hi = hi_;
-      asm volatile("" : "+v"(l31), "+v"(hi));
+      int lane = lane_;
+      asm volatile("" : "+v"(lane));
+      const int row = T::row(lane), pt = T::part(lane);
       const float *c_lds = reinterpret_cast<const float *>(smem + GEMM_LDS_LNW + bsel * 1024);
       const float inv_k = 1.f / (float)K;
-      float rs[4], nm[4];
+      float rs[T::NRB], nm[T::NRB];
 #pragma unroll
-      for (int mb = 0; mb < 4; ++mb) {
-        const float2 *sp = reinterpret_cast<const float2 *>(smem + GEMM_LDS_STATS + bsel * 8192) + (wm * 128 + mb * 32 + l31) * nparts;
+      for (int rb = 0; rb < T::NRB; ++rb) {
+        const float2 *sp = reinterpret_cast<const float2 *>(smem + GEMM_LDS_STATS + bsel * 8192) + (wm * 128 + rb * T::RB + row) * nparts;
         float t1 = 0.f, t2 = 0.f;
 #pragma unroll
         for (int i = 0; i < GEMM_LNF_MAXPARTS; ++i)
@@ -502,23 +535,21 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
             t2 += q.y;
           }
         const float mean = t1 * inv_k;
-        rs[mb] = rsqrtf(fmaxf(t2 * inv_k - mean * mean, 0.f) + ln_eps);
-        nm[mb] = -mean * rs[mb];
+        rs[rb] = rsqrtf(fmaxf(t2 * inv_k - mean * mean, 0.f) + ln_eps);
+        nm[rb] = -mean * rs[rb];
       }
 #pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
+      for (int cg = 0; cg < T::NCG; ++cg) {
+        const int nl = wn * 64 + T::col0(cg, pt);
+        const f32x4 cv = *reinterpret_cast<const f32x4 *>(c_lds + nl), dv = *reinterpret_cast<const f32x4 *>(bias_lds + nl);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int nl = wn * 64 + nb * 32 + 8 * g + 4 * hi;
-          const float4 cv = *reinterpret_cast<const float4 *>(c_lds + nl), dv = *reinterpret_cast<const float4 *>(bias_lds + nl);
+        for (int rb = 0; rb < T::NRB; ++rb) {
+          f32x4 v = T::get(acc, rb, cg);
 #pragma unroll
-          for (int mb = 0; mb < 4; ++mb) {
-            acc[nb][mb][4 * g + 0] = fmaf(rs[mb], acc[nb][mb][4 * g + 0], fmaf(nm[mb], cv.x, dv.x));
-            acc[nb][mb][4 * g + 1] = fmaf(rs[mb], acc[nb][mb][4 * g + 1], fmaf(nm[mb], cv.y, dv.y));
-            acc[nb][mb][4 * g + 2] = fmaf(rs[mb], acc[nb][mb][4 * g + 2], fmaf(nm[mb], cv.z, dv.z));
-            acc[nb][mb][4 * g + 3] = fmaf(rs[mb], acc[nb][mb][4 * g + 3], fmaf(nm[mb], cv.w, dv.w));
-          }
+          for (int e = 0; e < 4; ++e) v[e] = fmaf(rs[rb], v[e], fmaf(nm[rb], cv[e], dv[e]));
+          T::set(acc, rb, cg, v);
         }
+      }
     }
     if constexpr (EPI == 5) {
       // ---- residual epilogue: x = xres + acc on the fp32 residual stream in place, C = bf16(x), row partial sums of x.
@@ -528,8 +559,9 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
       // row-major: 16 lanes x 16 bytes = one row's 256 contiguous bytes per DPP row -- the load of the old x, the store of the new x
       // (2 full lines) and the bf16 store (1 full line) are all contiguous, and the row sums are DPP-row reductions.  Three rounds of
       // loads (12 KiB per wave) are kept in flight ahead of the staging.
-      int l31 = l31_, hi = hi_, lane = lane_;
-      asm volatile("" : "+v"(l31), "+v"(hi), "+v"(lane));
+      int lane = lane_;
+      asm volatile("" : "+v"(lane));
+      const int arow = T::row(lane), pt = T::part(lane);  // the lane's row of a row block and its quarter, as an accumulator owner
       char *cw = smem + par + (wave < 4 ? 8192 + (wave & 1) * 4096 + (wave >> 1) * 16384 : GEMM_OPBYTES + 4096 + (wave - 4) * 8192);
       const __amdgpu_buffer_rsrc_t x_rs = __builtin_amdgcn_make_buffer_rsrc(C2v, 0, (int)((size_t)M * N * 4), 0x00020000);
       const int r4 = lane >> 4, q = lane & 15;
@@ -575,16 +607,12 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
       float *const sh_lds = reinterpret_cast<float *>(smem + GEMM_LDS_SHIFT + wave * 512);
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
-        const int mb = r >> 1, h = r & 1;
-        if ((l31 >> 4) == h) {
+        // round r = row block r of the wave (16 rows x 64 columns = the staging slot): every lane writes its four column groups
+        static_assert(T::RB == 16, "a staging round of the residual epilogue is one row block");
 #pragma unroll
-          for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const int s16 = (nb * 8 + 2 * g + hi) ^ (l31 & 15);
-              *reinterpret_cast<float4 *>(cw + (l31 & 15) * 256 + s16 * 16) =
-                  make_float4(acc[nb][mb][4 * g + 0], acc[nb][mb][4 * g + 1], acc[nb][mb][4 * g + 2], acc[nb][mb][4 * g + 3]);
-            }
+        for (int cg = 0; cg < T::NCG; ++cg) {
+          const int s16 = (T::col0(cg, pt) >> 2) ^ arow;
+          *reinterpret_cast<f32x4 *>(cw + arow * 256 + s16 * 16) = T::get(acc, r, cg);
         }
         if (r == 0) {  // (here, behind the first staging writes: the x loads above stay in flight until now)
 #pragma unroll
@@ -623,7 +651,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
           a2 += dpp_f32<0x114, 0xF>(a2, 0.f);
           a1 += dpp_f32<0x118, 0xF>(a1, 0.f);
           a2 += dpp_f32<0x118, 0xF>(a2, 0.f);
-          if (q == 15) ln_part[((wm * 4 + mb) * 32 + h * 16 + row) * 4 + wn] = make_float2(a1, a2);
+          if (q == 15) ln_part[(wm * 128 + r * 16 + row) * 4 + wn] = make_float2(a1, a2);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -632,21 +660,22 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // (raw: the next tile's LDS-DMA stream stays in flight)
-      if (wn == 0 && hi == 0) {
+      if (wn == 0 && lane < 32) {  // (rows dealt over 32 lanes, four passes: nothing of the accumulator layout is left here)
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb) {
-          const float2 *pp = ln_part + ((wm * 4 + mb) * 32 + l31) * 4;
+          const float2 *pp = ln_part + (wm * 128 + mb * 32 + lane) * 4;
           const float4 p01 = *reinterpret_cast<const float4 *>(pp), p23 = *reinterpret_cast<const float4 *>(pp + 2);
           // (the stats buffer is padded to whole 256-row tiles: no bounds test)
-          stats[(size_t)(m0 + wm * 128 + mb * 32 + l31) * tiles_n + (n0 >> 8)] = make_float2((p01.x + p01.z) + (p23.x + p23.z), (p01.y + p01.w) + (p23.y + p23.w));
+          stats[(size_t)(m0 + wm * 128 + mb * 32 + lane) * tiles_n + (n0 >> 8)] = make_float2((p01.x + p01.z) + (p23.x + p23.z), (p01.y + p01.w) + (p23.y + p23.w));
         }
       }
     } else if constexpr (!F32) {
     // (lane-derived addresses recomputed per tile from laundered values: see the fp32-class epilogue below)
-    int l31 = l31_, hi = hi_, lane = lane_;
-    asm volatile("" : "+v"(l31), "+v"(hi), "+v"(lane));
-    // ---- epilogue: acc[nb][mb][4g + e] = C[m = wm*128 + mb*32 + l31][n = wn*64 + nb*32 + 8g + 4hi + e]
-    //      four passes of 32 rows per wave through a 4-KiB slot of the last K-tile's buffer (16-byte slots XOR-swizzled by
+    int lane = lane_;
+    asm volatile("" : "+v"(lane));
+    const int arow = T::row(lane), pt = T::part(lane);
+    // ---- epilogue: element e of T::get(acc, rb, cg) = C[m = wm*128 + rb*RB + arow][n = wn*64 + T::col0(cg, pt) + e]
+    //      four passes of 32 rows (32 / RB row blocks) per wave through a 4-KiB slot of the last K-tile's buffer (16-byte slots XOR-swizzled by
     //      row): waves 0-3 use the A1 half-tile slots, waves 4-7 the B1 slots -- the two the stream refills after the epilogue
     char *cw = smem + par + (wave < 4 ? 8192 + (wave & 1) * 4096 + (wave >> 1) * 16384 : GEMM_OPBYTES + 4096 + (wave - 4) * 8192);
     // stores go through a buffer descriptor: rows past M (ragged last tile) fall outside it and are dropped -- no branches
@@ -656,11 +685,13 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) {
 #pragma unroll
-      for (int nb = 0; nb < 2; ++nb) {
+      for (int j = 0; j < 32 / T::RB; ++j) {
+        const int rl = j * T::RB + arow;  // row within the pass
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int nl = nb * 32 + 8 * g + 4 * hi;  // local column of the 4 values
-          float v0 = acc[nb][mb][4 * g + 0], v1 = acc[nb][mb][4 * g + 1], v2 = acc[nb][mb][4 * g + 2], v3 = acc[nb][mb][4 * g + 3];
+        for (int cg = 0; cg < T::NCG; ++cg) {
+          const int nl = T::col0(cg, pt);  // local column of the 4 values
+          const f32x4 av = T::get(acc, mb * (32 / T::RB) + j, cg);
+          float v0 = av[0], v1 = av[1], v2 = av[2], v3 = av[3];
           if (EPI == 1 || EPI == 7) {
             v0 = gelu_bf16_class(v0);
             v1 = gelu_bf16_class(v1);
@@ -673,8 +704,8 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
             v2 = fmaxf(v2, 0.f);
             v3 = fmaxf(v3, 0.f);
           }
-          const int slot16 = (nl >> 3) ^ (l31 & 7);
-          *reinterpret_cast<uint2 *>(cw + l31 * 128 + slot16 * 16 + (nl & 4) * 2) = make_uint2(cvt_pk_bf16_f32(v0, v1), cvt_pk_bf16_f32(v2, v3));
+          const int slot16 = (nl >> 3) ^ (rl & 7);
+          *reinterpret_cast<uint2 *>(cw + rl * 128 + slot16 * 16 + (nl & 4) * 2) = make_uint2(cvt_pk_bf16_f32(v0, v1), cvt_pk_bf16_f32(v2, v3));
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -699,12 +730,14 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     } else {
-    // ---- fp32-class epilogue: acc[nb][mb][4g + e] = C[m = wm*128 + mb*32 + l31][n = wn*64 + nb*32 + 8g + 4hi + e] (bias already inside);
-    //      four passes (one per mb) of 32 rows x 64 columns per wave through 8 KiB of the last K-tile's buffer
+    // ---- fp32-class epilogue: element e of T::get(acc, rb, cg) = C[m = wm*128 + rb*RB + arow][n = wn*64 + T::col0(cg, pt) + e] (bias
+    //      already inside); four passes of 32 rows (32 / RB row blocks) x 64 columns per wave through 8 KiB of the last K-tile's buffer
     // (lane-derived LDS addresses below are recomputed per tile from laundered values: left loop-invariant, the compiler hoists ~30
     //  of them out of the TILE loop and they spill across the K loop)
-    int l31 = l31_, hi = hi_, lane = lane_;
-    asm volatile("" : "+v"(l31), "+v"(hi), "+v"(lane));
+    int lane = lane_;
+    asm volatile("" : "+v"(lane));
+    const int arow = T::row(lane), pt = T::part(lane);
+    constexpr int JB = 32 / T::RB;  // row blocks of a pass
     char *cw = smem + par + wave * 8192;
     // stores through buffer descriptors with 32-bit offsets: rows past M fall outside and are dropped (no branches, no 64-bit
     // address registers -- which spilled into the K loop)
@@ -715,28 +748,40 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
     // fp32 row-major and the split layout put (row m, 16-byte piece q of the wave's 64 columns) at the same byte offset
     const uint32_t c32_v0 = (uint32_t)((((size_t)m0 + wm * 128 + (lane >> 4)) * N + n0 + wn * 64 + (lane & 15) * 4) * 4);
     const uint32_t c16_v0 = (uint32_t)((((size_t)m0 + wm * 128 + (lane >> 3)) * N + n0 + wn * 64 + (lane & 7) * 8) * 2);
+    if (EPI == 1) {  // GELU on the accumulators in place, once for both output images
+#pragma unroll
+      for (int rb = 0; rb < T::NRB; ++rb)
+#pragma unroll
+        for (int cg = 0; cg < T::NCG; ++cg) {
+          f32x4 v = T::get(acc, rb, cg);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
+          T::set(acc, rb, cg, v);
+          __builtin_amdgcn_sched_barrier(0);  // one group at a time: interleaving many spills into the K loop
+        }
+    }
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) {
-      // the 4 values a lane holds of (nb, g); recomputed per output image instead of kept (32 registers) across both
-      auto vals = [&](int nb, int g, float (&x)[4]) {
+      // the 4 values a lane holds of column group cg of row block j of the pass
+      auto vals = [&](int j, int cg, float (&x)[4]) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float t = acc[nb][mb][4 * g + e];
-          if (EPI == 1) t = gelu_erf(t);
+          float t = T::get(acc, mb * JB + j, cg)[e];
           if (EPI == 2) t = fmaxf(t, 0.f);
           x[e] = t;
         }
         __builtin_amdgcn_sched_barrier(0);  // one group at a time: interleaving all 32 of a pass spills into the K loop
       };
       if (EPI == 4) {
-        // bf16 image: row = 128 B = 8 slots of 16 B (8 columns), slot nb * 4 + g, XOR-swizzled by the row
+        // bf16 image: row = 128 B = 8 slots of 16 B (8 columns), XOR-swizzled by the row
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
+        for (int j = 0; j < JB; ++j)
 #pragma unroll
-          for (int g = 0; g < 4; ++g) {
+          for (int cg = 0; cg < T::NCG; ++cg) {
             float x[4];
-            vals(nb, g, x);
-            *reinterpret_cast<uint2 *>(cw + l31 * 128 + (((nb * 4 + g) ^ (l31 & 7)) << 4) + hi * 8) =
+            vals(j, cg, x);
+            const int rl = j * T::RB + arow, nl = T::col0(cg, pt);
+            *reinterpret_cast<uint2 *>(cw + rl * 128 + (((nl >> 3) ^ (rl & 7)) << 4) + (nl & 4) * 2) =
                 make_uint2(cvt_pk_bf16_f32(x[0], x[1]), cvt_pk_bf16_f32(x[2], x[3]));
           }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -762,15 +807,15 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
         continue;
       }
       if (has_cf) {
-        // fp32 image: row = 256 B = 16 slots of 16 B, slot s = nb * 8 + 2 g + hi, XOR-swizzled by the row
+        // fp32 image: row = 256 B = 16 slots of 16 B (4 columns), XOR-swizzled by the row
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
+        for (int j = 0; j < JB; ++j)
 #pragma unroll
-          for (int g = 0; g < 4; ++g) {
+          for (int cg = 0; cg < T::NCG; ++cg) {
             float x[4];
-            vals(nb, g, x);
-            const int s = (nb * 8 + 2 * g + hi) ^ (l31 & 15);
-            *reinterpret_cast<float4 *>(cw + l31 * 256 + s * 16) = make_float4(x[0], x[1], x[2], x[3]);
+            vals(j, cg, x);
+            const int rl = j * T::RB + arow, s = (T::col0(cg, pt) >> 2) ^ (rl & 15);
+            *reinterpret_cast<float4 *>(cw + rl * 256 + s * 16) = make_float4(x[0], x[1], x[2], x[3]);
           }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -790,21 +835,23 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(127))) void 
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       }
       if (has_cs) {
-        // split image of the wave's 64 columns = 2 k-blocks of 128 B: block nb, element j = 8 g + 4 hi + e: hi part at byte
-        // nb * 128 + 2 j, lo part 64 bytes further; 16-byte slots XOR-swizzled by the row
+        // split image of the wave's 64 columns = 2 k-blocks of 128 B: column n = block n / 32, element n % 32: hi part at byte
+        // block * 128 + 2 element, lo part 64 bytes further; 16-byte slots XOR-swizzled by the row
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
+        for (int j = 0; j < JB; ++j)
 #pragma unroll
-          for (int g = 0; g < 4; ++g) {
+          for (int cg = 0; cg < T::NCG; ++cg) {
             float x[4];
-            vals(nb, g, x);
+            vals(j, cg, x);
+            const int rl = j * T::RB + arow, nl = T::col0(cg, pt);
             const uint32_t h0 = cvt_pk_bf16_f32(x[0], x[1]), h1 = cvt_pk_bf16_f32(x[2], x[3]);
             const float r0 = x[0] - __uint_as_float(h0 << 16), r1 = x[1] - __uint_as_float(h0 & 0xffff0000u);
             const float r2 = x[2] - __uint_as_float(h1 << 16), r3 = x[3] - __uint_as_float(h1 & 0xffff0000u);
             const uint32_t l0 = cvt_pk_bf16_f32(r0, r1), l1 = cvt_pk_bf16_f32(r2, r3);
-            const int sh = (nb * 8 + g) ^ (l31 & 15), sl = (nb * 8 + 4 + g) ^ (l31 & 15);  // slot of the hi / lo 16-byte chunk (8 elements)
-            *reinterpret_cast<uint2 *>(cw + l31 * 256 + sh * 16 + hi * 8) = make_uint2(h0, h1);
-            *reinterpret_cast<uint2 *>(cw + l31 * 256 + sl * 16 + hi * 8) = make_uint2(l0, l1);
+            const int s0 = (nl >> 5) * 8 + ((nl & 31) >> 3);
+            const int sh = s0 ^ (rl & 15), sl = (s0 + 4) ^ (rl & 15);  // slot of the hi / lo 16-byte chunk (8 elements)
+            *reinterpret_cast<uint2 *>(cw + rl * 256 + sh * 16 + (nl & 4) * 2) = make_uint2(h0, h1);
+            *reinterpret_cast<uint2 *>(cw + rl * 256 + sl * 16 + (nl & 4) * 2) = make_uint2(l0, l1);
           }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
