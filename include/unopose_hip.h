@@ -442,6 +442,26 @@ int unopose_add_layernorm_strided(const void *a, int a_bf16, const void *b, int 
                                   const float *bias, long rows, int C, float eps, void *out, int out_bf16,
                                   long ld_out, unopose_stream_t stream);
 
+/* Residual add + LayerNorm under autograd (the training step; float32 arithmetic).  C % 4 == 0, 4 <= C <= 1024, rows >= 0;
+ * every tensor rows x C row-major and contiguous, 16-byte aligned (bfloat16 inputs: 8-byte).
+ * _train: s = a (+ b) (a / b float32 or bfloat16 by flag, b may be NULL), y = LayerNorm(s) * w + bias; writes y and s
+ * (float32, rows x C) and the row statistics mean and rstd (float32, rows): mean first, then the centred sum of squares.
+ * _backward: from dy and the forward's s, mean, rstd: dx = rstd (g - mean_c(g) - xhat mean_c(g xhat)) with xhat = (s - mean) rstd,
+ * g = dy w: the gradient of a and of b.  With dw and db (both or neither): dw = sum_rows dy xhat, db = sum_rows dy, in two
+ * stages without atomics -- the rows are cut into unopose_add_layernorm_backward_slabs(rows, C) slabs of consecutive rows (a
+ * function of rows and C alone, <= 512 rows each); the workgroup that writes a slab's dx leaves one (2, C) partial in `partials`
+ * ((partial_slabs, 2, C) float32, partial_slabs >= that count); a second launch adds the partials in a fixed order: two calls
+ * give the same bits.
+ * dw == db == NULL: dx only, one launch, partials not touched (may be NULL). */
+int unopose_add_layernorm_train(const void *a, int a_bf16, const void *b, int b_bf16, const float *w,
+                                const float *bias, long rows, int C, float eps, float *y, float *s, float *mean,
+                                float *rstd, unopose_stream_t stream);
+/* number of row slabs (= partials) of the backward at this size; negative: outside the contract */
+int unopose_add_layernorm_backward_slabs(long rows, int C);
+int unopose_add_layernorm_backward(const float *dy, const float *s, const float *mean, const float *rstd,
+                                   const float *w, long rows, int C, float *dx, float *dw, float *db,
+                                   float *partials, int partial_slabs, unopose_stream_t stream);
+
 /* Pixel features at the chosen pixels only: bilinear resize (align_corners=False) of the 4x up-projected
  * ViT map to (H,W) fused with get_chosen_pixel_feats (oneref_feature_extraction.py:221-229,
  * utils/model_utils.py:215-227).  z (B,side,side,4,4,256) float32 or bfloat16 = the up-projection output

@@ -398,7 +398,7 @@ class _AttentionOutput(nn.Module):
         if x.is_cuda and not ops.is_differentiable():  # squeeze + residual + LayerNorm: one launch under autocast
             return ops.ffn_add_layernorm(x, self.expand, self.squeeze, self.norm, out=out)
         assert out is None
-        return self.norm(x + ops.linear(ops.linear(x, self.expand, relu=True), self.squeeze))
+        return ops.add_layernorm_train(x, ops.linear(ops.linear(x, self.expand, relu=True), self.squeeze), self.norm)
 
 
 class TransformerLayer(nn.Module):
@@ -418,8 +418,8 @@ class TransformerLayer(nn.Module):
         h = ops.token_attention(x, mem, a.attention, self.heads, embed)
         if x.is_cuda and not ops.is_differentiable():
             x = ops.linear_add_layernorm(h, a.linear, x, a.norm)
-        else:
-            x = a.norm(ops.linear(h, a.linear) + x)
+        else:  # under autograd on the GPU: residual add + LayerNorm on csrc/ln_train.hip (forward + backward); else the composite
+            x = ops.add_layernorm_train(ops.linear(h, a.linear), x, a.norm)
         return self.output(x, out=out)
 
 
@@ -503,8 +503,8 @@ class LinearTransformerLayer(nn.Module):
         h = ops.focused_linear_attention(x, mem, a.attention, self.heads, self.focusing_factor, kv_skip=kv_skip)
         if x.is_cuda and not ops.is_differentiable():
             x = ops.linear_add_layernorm(h, a.linear, x, a.norm)
-        else:
-            x = a.norm(ops.linear(h, a.linear) + x)
+        else:  # under autograd on the GPU: residual add + LayerNorm on csrc/ln_train.hip (forward + backward); else the composite
+            x = ops.add_layernorm_train(ops.linear(h, a.linear), x, a.norm)
         return self.output(x)
 
 

@@ -579,6 +579,77 @@ def add_layernorm(a, b, norm, out_dtype=None, out=None):
     return out
 
 
+class _AddLayerNormFn(torch.autograd.Function):
+    """LayerNorm(a + b) * weight + bias under autograd (csrc/ln_train.hip): a / b (..., C) fp32 or bf16 of one shape (b may be None),
+    weight / bias (C,) fp32; returns fp32.  Forward = the eval kernel's arithmetic, which also keeps s = a + b (fp32) and the rows' mean and
+    rstd; backward = one pass over dy and s that writes dx (the gradient of a and of b: rounded to bf16 for a bf16 input) and one (2, C)
+    partial of dweight / dbias per slab of rows, then a launch that adds the partials (skipped when neither is asked for).  No
+    atomics: two calls give the same bits."""
+
+    @staticmethod
+    def forward(ctx, a, b, weight, bias, eps):
+        a = _c(a)
+        C = a.shape[-1]
+        rows = a.numel() // C
+        if b is not None:
+            b = _c(b)
+            assert b.shape == a.shape
+        f32 = torch.float32
+        y, s = torch.empty(a.shape, dtype=f32, device=a.device), torch.empty(a.shape, dtype=f32, device=a.device)
+        mean, rstd = torch.empty(rows, dtype=f32, device=a.device), torch.empty(rows, dtype=f32, device=a.device)
+        with on_device(a.device):
+            call("unopose_add_layernorm_train", ptr(a), int(a.dtype == torch.bfloat16), ptr(b) if b is not None else None,
+                 int(b is not None and b.dtype == torch.bfloat16), ptr(weight), ptr(bias), rows, C, float(eps), ptr(y), ptr(s), ptr(mean), ptr(rstd),
+                 stream_ptr())
+        ctx.save_for_backward(s, mean, rstd, weight)
+        ctx.in_dtypes = (a.dtype, None if b is None else b.dtype)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        s, mean, rstd, weight = ctx.saved_tensors
+        C = s.shape[-1]
+        rows = s.numel() // C
+        dy = _c(dy if dy.dtype == torch.float32 else dy.float())
+        if dy.data_ptr() % 16:
+            dy = dy.clone()
+        dx = torch.empty_like(s)
+        params = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        dw = dbias = part = None
+        nslabs = 0
+        with on_device(s.device):
+            if params:
+                nslabs = lib().unopose_add_layernorm_backward_slabs(rows, C)
+                assert nslabs >= 0
+                dw, dbias = torch.empty(C, dtype=torch.float32, device=s.device), torch.empty(C, dtype=torch.float32, device=s.device)
+                part = torch.empty(max(nslabs, 1), 2, C, dtype=torch.float32, device=s.device)
+            call("unopose_add_layernorm_backward", ptr(dy), ptr(s), ptr(mean), ptr(rstd), ptr(weight), rows, C, ptr(dx),
+                 ptr(dw) if params else None, ptr(dbias) if params else None, ptr(part) if params else None, nslabs, stream_ptr())
+        da = dx.to(ctx.in_dtypes[0]) if ctx.needs_input_grad[0] else None
+        db = dx.to(ctx.in_dtypes[1]) if ctx.in_dtypes[1] is not None and ctx.needs_input_grad[1] else None
+        return da, db, dw if ctx.needs_input_grad[2] else None, dbias if ctx.needs_input_grad[3] else None, None
+
+
+def add_layernorm_train_ok(a, b, norm):
+    """`_AddLayerNormFn` applies: switch on, CUDA, fp32 / bf16 inputs of one shape, C % 4 == 0 in [4, 1024], an affine fp32 LayerNorm over C."""
+    ok = (torch.float32, torch.bfloat16)
+    C = a.shape[-1] if a.dim() else 0
+    w, bias = getattr(norm, "weight", None), getattr(norm, "bias", None)
+    return (st.TRAIN_OWN_LN and a.is_cuda and a.dtype in ok and C % 4 == 0 and 4 <= C <= 1024 and _aligned16(a)
+            and (b is None or (b.is_cuda and b.dtype in ok and b.shape == a.shape and b.device == a.device and _aligned16(b)))
+            and w is not None and bias is not None and w.dtype == torch.float32 and bias.dtype == torch.float32 and w.device == a.device
+            and tuple(norm.normalized_shape) == (C,))
+
+
+def add_layernorm_train(a, b, norm):
+    """norm(a + b) where autograd records it (the post-LN glue of the matcher's layers in the training step, transformer.py:151-193): on
+    `_AddLayerNormFn` when `add_layernorm_train_ok`, else the op-by-op composite."""
+    if add_layernorm_train_ok(a, b, norm):
+        return _AddLayerNormFn.apply(a, b, norm.weight, norm.bias, norm.eps)
+    return norm(a if b is None else a + b)
+
+
 def scale_residual_(x, y, gamma):
     """x (fp32, contiguous) += gamma * y (bf16) in place (ViT LayerScale residual)."""
     note_mutation()
