@@ -428,6 +428,10 @@ int unopose_vit_attention_f32_ss(const void *qkv_split, int B, int T, int H, voi
  * out (B,T,H*64) = softmax(q k^T / 8) v per head, flash-style.  qkv (B,T,3,H,64) = the fused qkv Linear
  * output; bfloat16 bit patterns. */
 int unopose_vit_attention(const void *qkv, int B, int T, int H, void *out, unopose_stream_t stream);
+/* The kernel unopose_vit_attention launches for a sequence length and head count (launches nothing): 0 = one 32-query block per wave,
+ * single chunk buffer (T < 512); 1 = two blocks per wave, double-buffered, 4 waves (T < 1024); 2 = the LDS-DMA kernel (T >= 1024);
+ * 3 = two blocks per wave, 8 waves (T >= 1024 and a qkv image of 2 GiB or more, past the DMA kernel's 32-bit offsets). */
+int unopose_vit_attention_route(int T, int H);
 
 /* out = LayerNorm(a (+ b)) * w + bias over the last dimension C (<= 1024), rows x C row-major.
  * a / b / out are float32 or bfloat16 (flags); b may be NULL.  One pass instead of the reference's

@@ -77,6 +77,7 @@ SIGNATURES = {
     "unopose_linear_wgrad_f32_splits": [ctypes.c_long, _I, _I],
     "unopose_linear_wgrad_f32": [_P, _P, ctypes.c_long, _I, _I, _P, _P, _P],
     "unopose_vit_attention": [_P, _I, _I, _I, _P, _P],
+    "unopose_vit_attention_route": [_I, _I],
     "unopose_add_layernorm": [_P, _I, _P, _I, _P, _P, ctypes.c_long, _I, _F, _P, _I, _P],
     "unopose_add_layernorm_strided": [_P, _I, _P, _I, _P, _P, ctypes.c_long, _I, _F, _P, _I, ctypes.c_long, _P],
     "unopose_add_layernorm_train": [_P, _I, _P, _I, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P],

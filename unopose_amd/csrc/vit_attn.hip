@@ -532,17 +532,30 @@ static int launch_vit_attn(const void *qkv, int B, int T, int H, void *out, hipS
   return check_launch("vit_attention");
 }
 
+// The one place that picks the kernel for a (T, H): 0 = vit_attn_kernel<1, 1, 4>, 1 = <2, 2, 4>, 2 = vit_attn_kernel_dma<4>, 3 = <2, 2, 8>.
+// tests/test_vit_attention_probes_gpu.py::test_dispatch_thresholds_are_where_the_probe_lengths_assume pins the thresholds (512, 1024, the
+// 2-GiB image) through unopose_vit_attention_route: its sequence lengths sit on both sides of each one, so whoever moves a threshold
+// re-chooses those lengths there.
+static int vit_attn_route(int T, int H) {
+  // T >= 1024: LDS-DMA staging, 4-wave workgroups, two per CU; a qkv image past 2 GiB per crop (32-bit DMA offsets): the register-staged kernel
+  if (T >= 1024) return (size_t)T * 3 * H * 64 * 2 < (1UL << 31) ? 2 : 3;
+  return T >= 512 ? 1 : 0;
+}
+
 extern "C" {
+
+int unopose_vit_attention_route(int T, int H) { return vit_attn_route(T, H); }
 
 int unopose_vit_attention(const void *qkv, int B, int T, int H, void *out, unopose_stream_t stream) {
   UNOPOSE_REQUIRE(qkv && out, "vit_attention: null pointer");
   UNOPOSE_REQUIRE(B >= 0 && T >= 1 && H >= 1 && (long)B * H * cdiv(T, 128) < (1L << 31), "vit_attention: bad sizes");
   if (B == 0) return UNOPOSE_OK;
-  // T >= 1024: LDS-DMA staging, 4-wave workgroups, two per CU; a qkv image past 2 GiB per crop (32-bit DMA offsets): the register-staged kernel
-  if (T >= 1024 && (size_t)T * 3 * H * 64 * 2 < (1UL << 31)) return launch_vit_attn_dma(qkv, B, T, H, out, (hipStream_t)stream);
-  if (T >= 1024) return launch_vit_attn<2, 2, 8>(qkv, B, T, H, out, (hipStream_t)stream);
-  if (T >= 512) return launch_vit_attn<2, 2, 4>(qkv, B, T, H, out, (hipStream_t)stream);
-  return launch_vit_attn<1, 1, 4>(qkv, B, T, H, out, (hipStream_t)stream);
+  switch (vit_attn_route(T, H)) {
+    case 3: return launch_vit_attn<2, 2, 8>(qkv, B, T, H, out, (hipStream_t)stream);
+    case 2: return launch_vit_attn_dma(qkv, B, T, H, out, (hipStream_t)stream);
+    case 1: return launch_vit_attn<2, 2, 4>(qkv, B, T, H, out, (hipStream_t)stream);
+    default: return launch_vit_attn<1, 1, 4>(qkv, B, T, H, out, (hipStream_t)stream);
+  }
 }
 
 }  // extern "C"

@@ -63,7 +63,9 @@ def vit_attention_torch(qkv, heads):
     C = C3 // 3
     hd = C // heads
     q, k, v = qkv.reshape(B, T, 3, heads, hd).permute(2, 0, 3, 1, 4)
-    a = torch.softmax((q * hd ** -0.5) @ k.transpose(-2, -1), dim=-1, dtype=torch.float32).to(v.dtype) @ v
+    # (softmax in fp32 for 16-bit inputs; float64 inputs stay float64 throughout -- tests/test_vit_attn_ref_cpu.py compares at 1e-12)
+    sm = torch.float64 if qkv.dtype == torch.float64 else torch.float32
+    a = torch.softmax((q * hd ** -0.5) @ k.transpose(-2, -1), dim=-1, dtype=sm).to(v.dtype) @ v
     return a.transpose(1, 2).reshape(B, T, C)
 
 
