@@ -518,6 +518,29 @@ int unopose_linear_attention_f32(const float *x, const float *inv_softplus_scale
                                  const float *ksum, int B, int N, int focus, int mode, float *out,
                                  unopose_stream_t stream);
 
+/* The same core under autograd (the float32 training step): forward and backward from the projections' outputs yq (B,N,256), yk and v
+ * (B,J,256) and s (256) = 1 / softplus(scale); 4 heads x 64, focus = 3, B <= 65535, N >= 1, J >= 1; every tensor float32, contiguous,
+ * 16-byte aligned.  Every product is a float32 FMA; every sum over rows is taken per workgroup and the partials are added in a
+ * fixed order by a second launch (no atomics): two calls give the same bits.
+ * _train: with q, k = the focused rows (q0 = (relu(y) + 1e-6) s, p = q0^3, q = p |q0| / |p|, norms over the 256 channels),
+ *   K (B,4,64 c,64 d) = sum_j k_jhc v_jhd, Kt (B,4,64 d,64 c) = its per-head transpose, S (B,256) = sum_j k_j,
+ *   den (B,N,4) = q_nh . S_h + 1e-6, out (B,N,256) = (q_nh K_h) / den_nh.
+ * _backward: from dout (B,N,256), the forward's inputs and K, Kt, S, den: dyq (B,N,256) and, all three or none, dyk, dv (B,J,256)
+ *   and ds (256) = the gradient of s over the query rows and the key rows of every batch.  All three NULL: one pass over the query
+ *   rows, the workspace is not touched (may be NULL).  A row whose input is <= 0 gets a gradient of exactly 0 there.
+ * partials: a workspace of partial_records records of unopose_linear_attention_f32_partial_floats() floats;
+ *   unopose_linear_attention_f32_partials(B, N, J) records serve both calls (negative: outside the contract).  It stays below
+ *   B N 256 floats from N = 512 on: a workgroup walks ceil(N / 8192) tiles of 128 query rows. */
+int unopose_linear_attention_f32_partial_floats(void);
+int unopose_linear_attention_f32_partials(int B, int N, int J);
+int unopose_linear_attention_f32_train(const float *yq, const float *yk, const float *v, const float *s, int B, int N, int J,
+                                       int focus, float *out, float *K, float *Kt, float *S, float *den, float *partials,
+                                       int partial_records, unopose_stream_t stream);
+int unopose_linear_attention_f32_backward(const float *dout, const float *yq, const float *yk, const float *v, const float *s,
+                                          const float *K, const float *Kt, const float *S, const float *den, int B, int N, int J,
+                                          int focus, float *dyq, float *dyk, float *dv, float *ds, float *partials,
+                                          int partial_records, unopose_stream_t stream);
+
 /* Depth maps of a triangle mesh in P poses (BOP's VSD error renders the object in the estimated and the ground-truth pose:
  * third_party/bop_toolkit/bop_toolkit_lib/pose_error.py:17-101, renderer.render_object(...)["depth"]).  verts (V,3) float32, faces (F,3)
  * int32, Rt (P,12) = row-major R then t (model -> camera, camera looks along +z), K4 (P,4) = fx, fy, cx, cy; integer pixel coordinates

@@ -40,3 +40,9 @@ for rnd in range(5):
 for v in (True, False):
     t = sorted(times[v])
     print(f"{dtype} {name}={v}: min {t[0]:.2f} median {t[len(t) // 2]:.2f} max {t[-1]:.2f} ms/step over {len(t)} steps: " + " ".join(f"{x:.1f}" for x in times[v]), flush=True)
+for v in (True, False):  # peak memory of one step per position
+    setattr(ops, name, v)
+    step()
+    torch.cuda.reset_peak_memory_stats()
+    step()
+    print(f"{dtype} {name}={v}: peak memory of a step {torch.cuda.max_memory_allocated() / 2 ** 20:.1f} MiB", flush=True)

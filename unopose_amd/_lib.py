@@ -90,6 +90,10 @@ SIGNATURES = {
     "unopose_linear_attention": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "unopose_linear_attention_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "unopose_linear_attention_kv_state": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "unopose_linear_attention_f32_partial_floats": [],
+    "unopose_linear_attention_f32_partials": [_I, _I, _I],
+    "unopose_linear_attention_f32_train": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P],
+    "unopose_linear_attention_f32_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "unopose_linear_bf16": [_P, _P, _P, _P, ctypes.c_long, _I, _I, _I, _P],
     "unopose_gemm_bf16_tile": [],
     "unopose_gemm_fold_stagger": [_I],

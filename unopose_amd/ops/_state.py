@@ -44,3 +44,4 @@ TRAIN_OWN_GEMM_MIN_FLOP = 4e9
 TRAIN_OWN_GEO = True  # round 6: the geometric embedding under autograd on the table kernels; False: the op-by-op composite
 TRAIN_OWN_ATTN = True  # the token attention core under autograd on csrc/attn_f32.hip (forward + backward kernels); False: the op-by-op composite
 TRAIN_OWN_LN = True  # residual add + LayerNorm under autograd on csrc/ln_train.hip (forward + backward kernels); False: the op-by-op composite
+TRAIN_OWN_LINATTN = True  # the focused linear attention core under autograd on csrc/linattn_train.hip (forward + backward kernels); False: the op-by-op composite

@@ -312,7 +312,10 @@ def focused_linear_attention(xq, xkv, att, heads, focusing, kv_skip=0):
     contraction + z scaling run in ONE HIP kernel per side (csrc/linattn.hip): bf16 MFMAs under autocast,
     hi/lo-split (fp32-class) MFMAs on fp32 data; other shapes take the op-by-op composite.
     `kv_skip`: leading rows of every batch of xkv that are not keys / values (xkv[:, kv_skip:] is meant; the bf16 kernels read the
-    window in place, the other paths slice)."""
+    window in place, the other paths slice).  Under autograd (differentiable mode, fp32) the core is `_LinearAttnFn` on the
+    projections' outputs (csrc/linattn_train.hip: forward and backward kernels); shapes outside it take the op-by-op composite."""
+    if st._DIFF and torch.is_grad_enabled() and linear_attention_train_ok(xq, xkv, att, heads, focusing):
+        return _focused_linear_attention_train(xq, xkv, att, kv_skip)
     if not st._DIFF and heads == 4 and xq.shape[-1] == 256 and xq.is_cuda and float(focusing) == 3.0:
         if torch.is_autocast_enabled():
             if kv_skip and not (st.USE_LA_KV_STATE and xkv.is_contiguous()):
@@ -326,6 +329,86 @@ def focused_linear_attention(xq, xkv, att, heads, focusing, kv_skip=0):
     if not st._DIFF and xq.is_cuda:
         note_fallback("focused_linear_attention", f"heads {heads} x width {xq.shape[-1]}, focusing {focusing} (kernels: 4 x 64, 3)")
     return focused_linear_attention_torch(xq, xkv, att, heads, focusing)
+
+
+_LA_PARTIAL_FLOATS = None
+
+
+def _la_workspace(B, N, J, device):
+    """The partial-sum workspace of the linear attention's training kernels at this size (records of a fixed number of floats)."""
+    global _LA_PARTIAL_FLOATS
+    if _LA_PARTIAL_FLOATS is None:
+        _LA_PARTIAL_FLOATS = lib().unopose_linear_attention_f32_partial_floats()
+    n = lib().unopose_linear_attention_f32_partials(B, N, J)
+    if n < 0:
+        raise RuntimeError(f"unopose_linear_attention_f32_partials: B={B} N={N} J={J} outside the contract")
+    return torch.empty(max(n, 1), _LA_PARTIAL_FLOATS, dtype=torch.float32, device=device), n
+
+
+class _LinearAttnFn(torch.autograd.Function):
+    """The core of `focused_linear_attention_torch` under autograd, from the projections' outputs: yq (B,N,256), yk / v (B,J,256) and
+    s (256) = 1 / softplus(scale) (a torch op of the caller's: the gradient of `scale` itself comes from autograd).  Forward =
+    csrc/linattn_train.hip's key state (K = k^T v per head, its transpose, S = sum_j k_j) and query pass, which keeps den (B,N,4);
+    backward = one pass over the query rows (dyq, per-workgroup partials of dK, dS, ds), one over the key rows (dyk, dv) and the
+    fixed-order sums of the partials.  The focused rows are recomputed, not stored: besides its inputs the function saves only
+    K, K^T, S and den.  Without a gradient for yk, v and s the backward is the query pass alone."""
+
+    @staticmethod
+    def forward(ctx, yq, yk, v, s):
+        B, N, C = yq.shape
+        J = yk.shape[1]
+        yq, yk, v, s = _c(yq), _c(yk), _c(v), _c(s)
+        dev = yq.device
+        out = torch.empty(B, N, C, dtype=torch.float32, device=dev)
+        K = torch.empty(B, 4, 64, 64, dtype=torch.float32, device=dev)
+        Kt = torch.empty_like(K)
+        S = torch.empty(B, C, dtype=torch.float32, device=dev)
+        den = torch.empty(B, N, 4, dtype=torch.float32, device=dev)
+        ws, n = _la_workspace(B, N, J, dev)
+        with on_device(dev):
+            call("unopose_linear_attention_f32_train", ptr(yq), ptr(yk), ptr(v), ptr(s), B, N, J, 3, ptr(out), ptr(K), ptr(Kt), ptr(S),
+                 ptr(den), ptr(ws), n, stream_ptr())
+        ctx.save_for_backward(yq, yk, v, s, K, Kt, S, den)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        yq, yk, v, s, K, Kt, S, den = ctx.saved_tensors
+        B, N, C = yq.shape
+        J = yk.shape[1]
+        dev = yq.device
+        dout = _c(dout.float())
+        keys = any(ctx.needs_input_grad[1:])
+        dyq = torch.empty_like(yq)
+        dyk = dv = ds = ws = None
+        n = 0
+        if keys:
+            dyk, dv, ds = torch.empty_like(yk), torch.empty_like(v), torch.empty_like(s)
+            ws, n = _la_workspace(B, N, J, dev)
+        with on_device(dev):
+            call("unopose_linear_attention_f32_backward", ptr(dout), ptr(yq), ptr(yk), ptr(v), ptr(s), ptr(K), ptr(Kt), ptr(S), ptr(den),
+                 B, N, J, 3, ptr(dyq), ptr(dyk) if keys else None, ptr(dv) if keys else None, ptr(ds) if keys else None,
+                 ptr(ws) if keys else None, n, stream_ptr())
+        need = ctx.needs_input_grad
+        return dyq if need[0] else None, dyk if need[1] else None, dv if need[2] else None, ds if need[3] else None
+
+
+def linear_attention_train_ok(xq, xkv, att, heads, focusing):
+    """`_LinearAttnFn` applies: switch on, CUDA, fp32 outside autocast, 4 heads x 64, focusing factor 3, at least one query and key."""
+    f32 = torch.float32
+    return (st.TRAIN_OWN_LINATTN and xq.is_cuda and heads == 4 and xq.shape[-1] == 256 and xkv.shape[-1] == 256 and float(focusing) == 3.0
+            and xq.shape[0] <= 65535 and xq.shape[1] >= 1 and xkv.shape[1] >= 1 and not torch.is_autocast_enabled()
+            and xq.dtype == f32 and xkv.dtype == f32 and att.proj_q.weight.dtype == f32 and att.scale.dtype == f32 and att.scale.numel() == 256)
+
+
+def _focused_linear_attention_train(xq, xkv, att, kv_skip=0):
+    """The projections as in the composite (trainable linears), s = 1 / softplus(scale) a torch op, the core on `_LinearAttnFn`;
+    `kv_skip` by slicing (autograd gives the skipped rows a zero gradient)."""
+    if kv_skip:
+        xkv = xkv[:, kv_skip:]
+    q, k, v = _lin(xq, att.proj_q), _lin(xkv, att.proj_k), _lin(xkv, att.proj_v)
+    s = (1.0 / F.softplus(att.scale)).reshape(-1)
+    return _LinearAttnFn.apply(q, k, v, s)
 
 
 def _focused_linear_attention_hip_f32(xq, xkv, att, focusing):
