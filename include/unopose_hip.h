@@ -908,6 +908,28 @@ int unopose_coloraug_step(const void *src, void *dst, int H, int W, const int *d
 int unopose_coloraug_blur_lines(const void *src, void *dst, int H, int W, const int *desc, const int *ops, int n_crops, int max_across,
                                 int max_line, int pos, int axis, unopose_stream_t stream);
 
+/* The match head of the training step without the (B, R, C) similarity (csrc/match_train.hip): for unit rows x (B, R, 256), y (B, C, 256)
+ * and S = tau x y^T (row / column 0 = the background token) everything the overlap losses need, from sweeps that recompute S tile by tile.
+ * _pad: row counts of the split planes are padded to a multiple of this.
+ * _split: x (B, N, 256) fp32 -> planes, 4 * B * Np * 256 uint16: [rows hi | rows lo] as (B, Np, 256), [transposed hi | lo] as (B, Np / 32, 256, 32);
+ *     hi = bf16(x), lo = bf16(x - hi); rows >= N are zero.  Np >= N, a multiple of _pad.  with_t == 0: only the two row planes (2 * B * Np * 256
+ *     uint16), all the forward and the row-side operand of the backward read.
+ * _forward: for the rows i = 1 .. R - 1 of x, all outputs (B, R - 1): L = logsumexp_{j >= 0} S_ij, F = logsumexp_{j >= 1} S_ij,
+ *     m = sum_{j >= 1} exp(S_ij - F_i) sv_j (sv (B, C - 1)), pred = an arg max over j >= 0 (may be null), picked = S_{i, lab_i} (lab (B, R - 1)
+ *     int32 in [0, C - 1]).  The column quantities are this call with (x, R) and (y, C) swapped.
+ * _backward: dX (B, R, 256) and dsr (B, R - 1) for the row-side operand (yplanes with the transposed planes), given the row vectors (Lr, Fr, mr = the forward's m, gr = the
+ *     upstream gradient of mr, sr = the scores of the rows, labr; all (B, R - 1)), the same for the columns ((B, C - 1)) and gL (B,) the
+ *     upstream gradient of the loss 0.5 (mean_i (Lr_i - picked_i) + mean_j (Lc_j - picked_j)); csrc/match_train.hip states G.  The column-side
+ *     gradients are this call with the operands and the two vector sets swapped.  No atomics; results depend on the shape alone. */
+int unopose_match_train_pad(void);
+int unopose_match_train_split(const float *x, int B, int N, int Np, int with_t, void *planes, unopose_stream_t stream);
+int unopose_match_train_forward(const void *xplanes, const void *yplanes, int B, int R, int Rp, int C, int Cp, float tau, const float *sv,
+                                const int *lab, float *L, float *F, float *m, int *pred, float *picked, unopose_stream_t stream);
+int unopose_match_train_backward(const void *xplanes, const void *yplanes, int B, int R, int Rp, int C, int Cp, float tau, const float *Lr,
+                                 const float *Fr, const float *mr, const float *gr, const float *sr, const int *labr, const float *Lc,
+                                 const float *Fc, const float *mc, const float *gc, const float *sc, const int *labc, const float *gL,
+                                 float *dX, float *dsr, unopose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,40 +52,52 @@ def overlap_losses(end_points, atten_list, score_list, saliency_list, pts1, pts2
                                predator_thres, dis_thres, prefix)
 
 
-def _overlap_losses(end_points, atten_list, score_list, saliency_list, pts1, pts2, gt_R, gt_t, predator_thres, dis_thres, prefix):
-    n1 = pts1.shape[1]
+def match_targets(pts1, pts2, gt_R, gt_t, predator_thres=0.15, dis_thres=0.15, dtype=torch.float32):
+    """The targets of `overlap_losses`, which depend on the points and the ground truth alone (loss_utils.py:150-176): the query points in
+    the reference frame, the overlap indicator (B, n1 + n2) as `dtype`, and the nearest partner of every point as its class label
+    (l1 (B, n1) in [0, n2], l2 (B, n2) in [0, n1]; 0 = background, no partner within dis_thres).  fp32 inputs."""
     in_ref = (pts1 - gt_t.unsqueeze(1)) @ gt_R  # query points expressed in the reference frame
-    fused = in_ref.is_cuda and FUSED_LABELS
-    if fused:
+    if in_ref.is_cuda and FUSED_LABELS:
         # csrc/glue.hip: nearest partner and "any partner close" per point, both directions, without the (B, n1, n2) matrix
         from . import ops
 
         d1, nn1, any1 = ops.nearest_partner(in_ref, pts2, predator_thres, over_b=True)
         d2, nn2, any2 = ops.nearest_partner(in_ref, pts2, predator_thres, over_b=False)
-        overlap = torch.cat([any1, any2], 1).to(score_list[0].dtype)
+        overlap = torch.cat([any1, any2], 1).to(dtype)
     else:
         dist = torch.sqrt(_pairwise_sq_dist(in_ref, pts2))  # (B, n1, n2)
         close = dist <= predator_thres
-        overlap = torch.cat([close.any(2), close.any(1)], 1).to(score_list[0].dtype)  # a point overlaps if ANY partner is close
-    for i, score in enumerate(score_list):
-        end_points[f"{prefix}_score_loss{i}"] = weighted_bce(score.float(), overlap)
-    for i, sal in enumerate(saliency_list):
-        end_points[f"{prefix}_saliency_loss{i}"] = weighted_bce(sal.float(), overlap)
-    # nearest partner as the class label, 0 = background (no partner within dis_thres)
-    if not fused:
+        overlap = torch.cat([close.any(2), close.any(1)], 1).to(dtype)  # a point overlaps if ANY partner is close
         d1, nn1 = dist.min(2)
         d2, nn2 = dist.min(1)
     label1 = torch.where(d1 <= dis_thres, nn1 + 1, torch.zeros_like(nn1))
     label2 = torch.where(d2 <= dis_thres, nn2 + 1, torch.zeros_like(nn2))
-    for i, atten in enumerate(atten_list):
-        end_points[f"{prefix}_atten_loss{i}"] = _infonce(atten, label1, label2)
-    pred = atten_list[-1][:, 1:, :].max(dim=2)[1]
+    return {"in_ref": in_ref, "overlap": overlap, "l1": label1, "l2": label2}
+
+
+def fill_match_losses(end_points, targets, atten_losses, score_list, saliency_list, pred, pts2, prefix):
+    """The `end_points` entries of `overlap_losses` from per-block (correspondence loss (B,), score, saliency), the last block's row arg max
+    `pred` (B, n1) over all columns, and `match_targets`' result."""
+    overlap, label1, in_ref = targets["overlap"], targets["l1"], targets["in_ref"]
+    for i, score in enumerate(score_list):
+        end_points[f"{prefix}_score_loss{i}"] = weighted_bce(score.float(), overlap)
+    for i, sal in enumerate(saliency_list):
+        end_points[f"{prefix}_saliency_loss{i}"] = weighted_bce(sal.float(), overlap)
+    for i, loss in enumerate(atten_losses):
+        end_points[f"{prefix}_atten_loss{i}"] = loss
     fg = (pred > 0).float()
     end_points[f"{prefix}_acc"] = (pred == label1).float().mean(1)
     end_points[f"{prefix}_fg_num"] = fg.sum(1)
     partner = torch.gather(pts2, 1, (fg * (pred - 1)).long().unsqueeze(2).expand(-1, -1, 3))
     end_points[f"{prefix}_dis"] = (torch.norm(partner - in_ref, dim=2) * fg).sum(1) / (fg.sum(1) + 1e-8)
     return end_points
+
+
+def _overlap_losses(end_points, atten_list, score_list, saliency_list, pts1, pts2, gt_R, gt_t, predator_thres, dis_thres, prefix):
+    tg = match_targets(pts1, pts2, gt_R, gt_t, predator_thres, dis_thres, score_list[0].dtype)
+    losses = [_infonce(atten, tg["l1"], tg["l2"]) for atten in atten_list]
+    pred = atten_list[-1][:, 1:, :].max(dim=2)[1]
+    return fill_match_losses(end_points, tg, losses, score_list, saliency_list, pred, pts2, prefix)
 
 
 def process_loss(end_points):

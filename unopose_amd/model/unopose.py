@@ -10,7 +10,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from ..losses import aug_pose_noise, overlap_losses
+from ..losses import aug_pose_noise, fill_match_losses, match_targets, overlap_losses
 from .config import to_cfg
 from .modules import (GeometricStructureEmbedding, GeometricTransformer, PositionalEncoding,
                       SparseToDenseTransformer, ViTEncoderOneRef, _adjacent)
@@ -44,16 +44,45 @@ def _bg_row(mod, dtype):
     return c[1]
 
 
-def _block_outputs(out_proj, score_head, f1, f2, n1, temp):
+def _block_outputs(out_proj, score_head, f1, f2, n1, temp, targets=None, want_pred=False):
     """What the training branch keeps per transformer block (C:62-76, Fi:85-99): the similarity of the projected
-    features, the overlap scores and the saliency = overlap scores propagated through the row / column softmax."""
+    features, the overlap scores and the saliency = overlap scores propagated through the row / column softmax.
+    -> (atten, score, saliency, None).  With `targets` (losses.match_targets) and inputs ops.match_head admits, the block's
+    correspondence loss, saliency and row arg max come from the features without the similarity (csrc/match_train.hip):
+    -> (None, score, saliency, (loss, pred or None))."""
     scores = score_head(torch.cat((f1, f2), dim=1))
-    atten = ops.feature_similarity(ops.linear(f1, out_proj), ops.linear(f2, out_proj), temp)
     s1, s2 = scores[:, 1:(n1 + 1)], scores[:, (n1 + 2):]
-    m1, m2 = ops.saliency_pair(atten, s1, s2)  # softmax(atten[:, 1:, 1:]) @ s2 and its transposed twin (csrc/saliency_train.hip under train())
+    o1, o2 = ops.linear(f1, out_proj), ops.linear(f2, out_proj)
     score = torch.clamp(torch.sigmoid(torch.cat((s1, s2), dim=1).squeeze(-1)), min=0, max=1)
+    if targets is not None:
+        a, b = F.normalize(o1, p=2, dim=2), F.normalize(o2, p=2, dim=2)
+        loss, m1, m2, pred = ops.match_head(a, b, s1, s2, targets["l1"], targets["l2"], 1.0 / temp, want_pred)
+        saliency = torch.clamp(torch.sigmoid(torch.cat((m1, m2), dim=1).squeeze(-1)), min=0, max=1)
+        return None, score, saliency, (loss, pred)
+    atten = ops.feature_similarity(o1, o2, temp)
+    m1, m2 = ops.saliency_pair(atten, s1, s2)  # softmax(atten[:, 1:, 1:]) @ s2 and its transposed twin (csrc/saliency_train.hip under train())
     saliency = torch.clamp(torch.sigmoid(torch.cat((m1, m2), dim=1).squeeze(-1)), min=0, max=1)
-    return atten, score, saliency
+    return atten, score, saliency, None
+
+
+def _match_targets(mod, f1, f2, p1, p2, gt_R, gt_t):
+    """The loss targets ahead of the block loop when the blocks' match heads run on ops.match_head (fp32 CUDA features outside autocast, a
+    256-wide projection, ops.TRAIN_OWN_MATCH), else None: `overlap_losses` then computes them from the similarities as before."""
+    if not (ops.TRAIN_OWN_MATCH and mod.out_proj.out_features == 256 and f1.dtype == torch.float32 and f2.dtype == torch.float32
+            and mod.out_proj.weight.dtype == torch.float32 and 1 <= f1.shape[0] <= 65535 and p1.shape[1] >= 1 and p2.shape[1] >= 1
+            and f1.is_cuda and p1.is_cuda and not torch.is_autocast_enabled()):
+        return None
+    return match_targets(p1.float(), p2.float(), gt_R.float(), gt_t.float(), mod.cfg.loss_predator_thres, mod.cfg.loss_dis_thres)
+
+
+def _block_losses(mod, end_points, outs, targets, p1, p2, gt_R, gt_t, prefix):
+    """The per-block outputs of `_block_outputs` -> the `<prefix>_*` entries of end_points (loss_utils.py:132-203)."""
+    scores, sals = [o[1] for o in outs], [o[2] for o in outs]
+    if targets is None:
+        return overlap_losses(end_points, [o[0] for o in outs], scores, sals, p1, p2, gt_R, gt_t, mod.cfg.loss_predator_thres,
+                              mod.cfg.loss_dis_thres, prefix)
+    return fill_match_losses(end_points, targets, [o[3][0] for o in outs], [s.float() for s in scores], [s.float() for s in sals],
+                             outs[-1][3][1], p2.float(), prefix)
 
 
 class CoarsePointMatchingOneRef(nn.Module):
@@ -76,18 +105,15 @@ class CoarsePointMatchingOneRef(nn.Module):
         bg = self.bg_token.expand(B, -1, -1)
         f1 = torch.cat([bg, ops.linear(f1, self.in_proj)], dim=1)
         f2 = torch.cat([bg, ops.linear(f2, self.in_proj)], dim=1)
-        attens, scores, sals = [], [], []
-        for blk, head in zip(self.transformers, self.score_heads):
-            f1, f2 = blk(f1, geo1, f2, geo2)
-            a, sc, sa = _block_outputs(self.out_proj, head, f1, f2, n1, self.cfg.temp)
-            attens.append(a)
-            scores.append(sc)
-            sals.append(sa)
         gt_R = end_points["rotation_label"]
         gt_t = end_points["translation_label"] / (radius.reshape(-1, 1) + 1e-6)
+        targets = _match_targets(self, f1, f2, p1, p2, gt_R, gt_t)  # (the labels depend on the points and the ground truth only)
+        outs = []
+        for i, (blk, head) in enumerate(zip(self.transformers, self.score_heads)):
+            f1, f2 = blk(f1, geo1, f2, geo2)
+            outs.append(_block_outputs(self.out_proj, head, f1, f2, n1, self.cfg.temp, targets, i == self.nblock - 1))
         init_R, init_t = end_points["aug_pose"] if "aug_pose" in end_points else aug_pose_noise(gt_R, gt_t)
-        overlap_losses(end_points, attens, scores, sals, p1, p2, gt_R, gt_t, self.cfg.loss_predator_thres,
-                       self.cfg.loss_dis_thres, "coarse_hard")
+        _block_losses(self, end_points, outs, targets, p1, p2, gt_R, gt_t, "coarse_hard")
         end_points["init_R"], end_points["init_t"] = init_R, init_t
         return end_points
 
@@ -164,17 +190,14 @@ class FinePointMatchingOneRef(nn.Module):
             pe1, pe2 = self.PE.project(g1), self.PE.project(g2)
         f1 = torch.cat([bg, ops.linear(f1, self.in_proj) + pe1], dim=1)
         f2 = torch.cat([bg, ops.linear(f2, self.in_proj) + pe2], dim=1)
-        attens, scores, sals = [], [], []
-        for blk, head in zip(self.transformers, self.score_heads):
-            f1, f2 = blk(f1, geo1, fps_idx1, f2, geo2, fps_idx2)
-            a, sc, sa = _block_outputs(self.out_proj, head, f1, f2, n1, self.cfg.temp)
-            attens.append(a)
-            scores.append(sc)
-            sals.append(sa)
         gt_R = end_points["rotation_label"]
         gt_t = end_points["translation_label"] / (radius.reshape(-1, 1) + 1e-6)
-        overlap_losses(end_points, attens, scores, sals, p1, p2, gt_R, gt_t, self.cfg.loss_predator_thres,
-                       self.cfg.loss_dis_thres, "fine")
+        targets = _match_targets(self, f1, f2, p1, p2, gt_R, gt_t)
+        outs = []
+        for i, (blk, head) in enumerate(zip(self.transformers, self.score_heads)):
+            f1, f2 = blk(f1, geo1, fps_idx1, f2, geo2, fps_idx2)
+            outs.append(_block_outputs(self.out_proj, head, f1, f2, n1, self.cfg.temp, targets, i == self.nblock - 1))
+        _block_losses(self, end_points, outs, targets, p1, p2, gt_R, gt_t, "fine")
         return end_points
 
     def forward(self, p1, f1, geo1, fps_idx1, p2, f2, geo2, fps_idx2, radius, end_points, pe2_groups=None):

@@ -45,3 +45,4 @@ TRAIN_OWN_GEO = True  # round 6: the geometric embedding under autograd on the t
 TRAIN_OWN_ATTN = True  # the token attention core under autograd on csrc/attn_f32.hip (forward + backward kernels); False: the op-by-op composite
 TRAIN_OWN_LN = True  # residual add + LayerNorm under autograd on csrc/ln_train.hip (forward + backward kernels); False: the op-by-op composite
 TRAIN_OWN_LINATTN = True  # the focused linear attention core under autograd on csrc/linattn_train.hip (forward + backward kernels); False: the op-by-op composite
+TRAIN_OWN_MATCH = True  # the match head (InfoNCE + saliency + arg max of a block) under autograd on csrc/match_train.hip, no (B, R, C) similarity; False: the composite over the materialised matrix

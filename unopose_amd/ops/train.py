@@ -1,5 +1,5 @@
-"""Autograd Functions of the training step on own kernels: InfoNCE, BatchNorm + ReLU (+ max-pool), saliency, nearest partner, the PE's 1 x 1
-convolutions (csrc/bn_train.hip, conv_train.hip, saliency_train.hip)."""
+"""Autograd Functions of the training step on own kernels: InfoNCE, BatchNorm + ReLU (+ max-pool), saliency, the match head without the
+similarity matrix, nearest partner, the PE's 1 x 1 convolutions (csrc/bn_train.hip, conv_train.hip, saliency_train.hip, match_train.hip)."""
 import torch
 import torch.nn.functional as F
 
@@ -197,6 +197,108 @@ def saliency_pair(atten, s1, s2):
         return _SaliencyFn.apply(atten, s1, s2)
     inner = atten[:, 1:, 1:]
     return torch.matmul(F.softmax(inner, dim=2), s2), torch.matmul(F.softmax(inner.transpose(1, 2), dim=2), s1)
+
+
+def _match_split(x, with_t):
+    """x (B, N, 256) fp32 -> (the bf16 hi / lo planes of csrc/match_train.hip, by rows and -- `with_t` -- transposed, as one int16 tensor;
+    padded N)."""
+    B, N = x.shape[:2]
+    pad = lib().unopose_match_train_pad()
+    Np = (N + pad - 1) // pad * pad
+    planes = torch.empty((4 if with_t else 2) * B * Np * 256, dtype=torch.int16, device=x.device)
+    call("unopose_match_train_split", ptr(x), B, N, Np, int(with_t), ptr(planes), stream_ptr())
+    return planes, Np
+
+
+class _MatchHeadFn(torch.autograd.Function):
+    """The match head of one transformer block from the unit-normalised projected features a (B, 1 + n1, 256), b (B, 1 + n2, 256) -- the
+    InfoNCE loss of S = inv_temp a b^T, the saliency pair of (S, s1, s2) and the row arg max -- on csrc/match_train.hip: a row sweep and a
+    column sweep forward, the same two backward; S is recomputed tile by tile and never stored.  Saved for backward: a and b themselves (the
+    split planes are rebuilt there: two small launches instead of 2 x their size kept per block), the statistics vectors (L, F, m per row
+    and per column), s1 / s2 and the int32 labels."""
+
+    @staticmethod
+    def forward(ctx, a, b, s1, s2, l1, l2, inv_temp, want_pred):
+        B, R, C = a.shape[0], a.shape[1], b.shape[1]
+        n1, n2 = R - 1, C - 1
+        dev = a.device
+        v1, v2 = _c(s1.detach().reshape(B, n1)), _c(s2.detach().reshape(B, n2))
+        i1, i2 = _c(l1.to(torch.int32)), _c(l2.to(torch.int32))
+        tau = float(inv_temp)
+        Lr, Fr, m1, pr = (torch.empty(B, n1, dtype=torch.float32, device=dev) for _ in range(4))
+        Lc, Fc, m2, pc = (torch.empty(B, n2, dtype=torch.float32, device=dev) for _ in range(4))
+        pred = torch.empty(B, n1, dtype=torch.int32, device=dev) if want_pred else None
+        a, b = _c(a.detach()), _c(b.detach())
+        with on_device(dev):
+            pa, Rp = _match_split(a, False)
+            pb, Cp = _match_split(b, False)
+            call("unopose_match_train_forward", ptr(pa), ptr(pb), B, R, Rp, C, Cp, tau, ptr(v2), ptr(i1), ptr(Lr), ptr(Fr), ptr(m1),
+                 ptr(pred) if want_pred else None, ptr(pr), stream_ptr())
+            call("unopose_match_train_forward", ptr(pb), ptr(pa), B, C, Cp, R, Rp, tau, ptr(v1), ptr(i2), ptr(Lc), ptr(Fc), ptr(m2), None, ptr(pc),
+                 stream_ptr())
+        loss = 0.5 * ((Lr - pr).mean(1) + (Lc - pc).mean(1))
+        ctx.save_for_backward(a, b, v1, v2, i1, i2, Lr, Fr, m1, Lc, Fc, m2)
+        ctx.meta = (B, R, C, tau, s1.shape, s2.shape)
+        out_pred = pred.long() if want_pred else None
+        if want_pred:
+            ctx.mark_non_differentiable(out_pred)
+        return loss, m1.reshape(B, n1, 1), m2.reshape(B, n2, 1), out_pred
+
+    @staticmethod
+    def backward(ctx, gL, g1, g2, _gpred):
+        a, b, v1, v2, i1, i2, Lr, Fr, m1, Lc, Fc, m2 = ctx.saved_tensors
+        B, R, C, tau, sh1, sh2 = ctx.meta
+        need_a, need_b, need_s1, need_s2 = ctx.needs_input_grad[:4]
+        rows, cols = need_a or need_s1, need_b or need_s2
+        dev = a.device
+        gL, g1, g2 = _c(gL.float()), _c(g1.float().reshape(B, R - 1)), _c(g2.float().reshape(B, C - 1))
+        da = db = ds1 = ds2 = None
+        with on_device(dev):
+            pa, Rp = _match_split(a, cols)  # (the transposed planes of an operand are read by the OTHER side's launch)
+            pb, Cp = _match_split(b, rows)
+            if rows:
+                da = torch.empty(B, R, 256, dtype=torch.float32, device=dev)
+                ds1 = torch.empty(B, R - 1, dtype=torch.float32, device=dev)
+                call("unopose_match_train_backward", ptr(pa), ptr(pb), B, R, Rp, C, Cp, tau, ptr(Lr), ptr(Fr), ptr(m1), ptr(g1), ptr(v1), ptr(i1),
+                     ptr(Lc), ptr(Fc), ptr(m2), ptr(g2), ptr(v2), ptr(i2), ptr(gL), ptr(da), ptr(ds1), stream_ptr())
+            if cols:
+                db = torch.empty(B, C, 256, dtype=torch.float32, device=dev)
+                ds2 = torch.empty(B, C - 1, dtype=torch.float32, device=dev)
+                call("unopose_match_train_backward", ptr(pb), ptr(pa), B, C, Cp, R, Rp, tau, ptr(Lc), ptr(Fc), ptr(m2), ptr(g2), ptr(v2), ptr(i2),
+                     ptr(Lr), ptr(Fr), ptr(m1), ptr(g1), ptr(v1), ptr(i1), ptr(gL), ptr(db), ptr(ds2), stream_ptr())
+        return (da if need_a else None, db if need_b else None, ds1.reshape(sh1) if need_s1 else None, ds2.reshape(sh2) if need_s2 else None,
+                None, None, None, None)
+
+
+def _match_head_domain(a, b, s1, s2, l1, l2):
+    """The domain of csrc/match_train.hip: fp32 CUDA tensors outside autocast, feature width 256, contiguous and 16-byte aligned features,
+    at least one point per cloud."""
+    if not (a.is_cuda and b.is_cuda and not torch.is_autocast_enabled()):
+        return False
+    if not (a.dim() == 3 and b.dim() == 3 and a.shape[0] == b.shape[0] and a.shape[2] == 256 and b.shape[2] == 256):
+        return False
+    B, n1, n2 = a.shape[0], a.shape[1] - 1, b.shape[1] - 1
+    return (n1 >= 1 and n2 >= 1 and 1 <= B <= 65535 and all(t.dtype == torch.float32 and t.is_cuda for t in (a, b, s1, s2))
+            and a.is_contiguous() and b.is_contiguous() and _aligned16(a) and _aligned16(b)
+            and s1.numel() == B * n1 and s2.numel() == B * n2 and tuple(l1.shape) == (B, n1) and tuple(l2.shape) == (B, n2)
+            and l1.is_cuda and l2.is_cuda and not l1.dtype.is_floating_point and not l2.dtype.is_floating_point)
+
+
+def match_head_train_ok(a, b, s1, s2, l1, l2):
+    """`_MatchHeadFn` applies in the training step: switch on, CUDA, fp32 outside autocast, feature width 256, 16-byte aligned contiguous
+    features, n1 and n2 >= 1."""
+    return st.TRAIN_OWN_MATCH and _match_head_domain(a, b, s1, s2, l1, l2)
+
+
+def match_head(a, b, s1, s2, l1, l2, inv_temp, want_pred=False):
+    """(loss (B,), m1 (B, n1, 1), m2 (B, n2, 1), pred (B, n1) or None) of one transformer block from the UNIT rows a (B, 1 + n1, 256),
+    b (B, 1 + n2, 256) (row 0 = the background token), the overlap logits s1 (B, n1, 1), s2 (B, n2, 1) and the labels l1 (B, n1) in
+    [0, n2], l2 (B, n2) in [0, n1] (0 = background): with S = inv_temp a b^T, loss = infonce_two_way(S, l1, l2), (m1, m2) =
+    saliency_pair(S, s1, s2), pred = S[:, 1:, :].max(2)[1] -- without S (csrc/match_train.hip).  `match_head_train_ok` is the training step's guard;
+    inputs outside the kernels' domain are an error here."""
+    if not _match_head_domain(a, b, s1, s2, l1, l2):
+        raise RuntimeError("match_head: inputs outside the kernels' domain (see match_head_train_ok)")
+    return _MatchHeadFn.apply(a, b, s1, s2, l1, l2, inv_temp, want_pred)
 
 
 def nearest_partner(a, b, thr, over_b=True):
