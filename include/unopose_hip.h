@@ -291,6 +291,26 @@ int unopose_conv1x1_train_wgrad(const float *dy, const float *x, int B, int cout
  * workspace = unopose_linear_wgrad_f32_splits(rows, N, K) * N * K floats. */
 int unopose_linear_wgrad_f32_splits(long rows, int N, int K);
 int unopose_linear_wgrad_f32(const float *g, const float *x, long rows, int N, int K, float *workspace, float *dw, unopose_stream_t stream);
+
+/* The small trainable nn.Linear layers of the matcher under autograd (torch.nn.functional.linear [+ relu] and its backward), straight from
+ * the float32 row-major tensors as stored: x (rows, K), w (N, K), g and y (rows, N); every pointer 16-byte aligned.  Domain:
+ * 1 <= rows <= 16383, N and K multiples of 64 in [64, 512].  Outside it, with a null pointer or a workspace that is too small: an error, nothing written.
+ *   forward: y = act(x w^T + bias), act = ReLU when relu != 0; bias may be NULL.
+ *   dx:      dx = (g . [y > 0]) w  (y NULL: no mask); w is read as stored, the contraction runs over N.
+ *   dwdb:    dw = (g . [y > 0])^T x and db = sum over the rows of (g . [y > 0]) (db may be NULL) in one launch plus one combining launch.
+ *   backward: dx, dw and db together: the work of `dx` and `dwdb` in ONE launch (same arithmetic, same bits) plus the combining launch.
+ * y and dx: fp32 class (bf16 hi / lo split inside the kernel, three MFMAs per product, fp32 accumulation).  dw and db: exact fp32 products
+ * and accumulation over row slices whose number and bounds depend on (rows, N, K) alone, combined in double in slice order (no atomics:
+ * two calls give the same bits).  workspace: unopose_linear_small_train_ws_floats(rows, N, K) floats (-1 outside the domain),
+ * `workspace_floats` = the floats the caller really holds. */
+int unopose_linear_small_train_ws_floats(long rows, int N, int K);
+int unopose_linear_small_train_forward(const float *x, const float *w, const float *bias, long rows, int N, int K, int relu, float *y,
+                                       unopose_stream_t stream);
+int unopose_linear_small_train_dx(const float *g, const float *y, const float *w, long rows, int N, int K, float *dx, unopose_stream_t stream);
+int unopose_linear_small_train_dwdb(const float *g, const float *y, const float *x, long rows, int N, int K, float *workspace, long workspace_floats,
+                                    float *dw, float *db, unopose_stream_t stream);
+int unopose_linear_small_train_backward(const float *g, const float *y, const float *x, const float *w, long rows, int N, int K, float *workspace,
+                                        long workspace_floats, float *dx, float *dw, float *db, unopose_stream_t stream);
 int unopose_assign_labels(const float *atten, int B, int R, int C, const float *score1,
                           const float *score2, float *stats_ws, float *w1, float *w2,
                           unopose_stream_t stream);

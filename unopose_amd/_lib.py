@@ -80,6 +80,11 @@ SIGNATURES = {
     "unopose_conv1x1_train_wgrad": [_P, _P, _I, _I, _I, ctypes.c_long, _P, _P, _P],
     "unopose_linear_wgrad_f32_splits": [ctypes.c_long, _I, _I],
     "unopose_linear_wgrad_f32": [_P, _P, ctypes.c_long, _I, _I, _P, _P, _P],
+    "unopose_linear_small_train_ws_floats": [_L, _I, _I],
+    "unopose_linear_small_train_forward": [_P, _P, _P, _L, _I, _I, _I, _P, _P],
+    "unopose_linear_small_train_dx": [_P, _P, _P, _L, _I, _I, _P, _P],
+    "unopose_linear_small_train_dwdb": [_P, _P, _P, _L, _I, _I, _P, _L, _P, _P, _P],
+    "unopose_linear_small_train_backward": [_P, _P, _P, _P, _L, _I, _I, _P, _L, _P, _P, _P, _P],
     "unopose_vit_attention": [_P, _I, _I, _I, _P, _P],
     "unopose_vit_attention_route": [_I, _I],
     "unopose_add_layernorm": [_P, _I, _P, _I, _P, _P, ctypes.c_long, _I, _F, _P, _I, _P],

@@ -23,7 +23,7 @@ from .common import (  # noqa: F401
 )
 from .dense import (  # noqa: F401
     linear_backend, _bf16_weights, linear_bf16_hip, own_gemm_ok, bf16_linear_2d, f32x3_ok, split_f32, _f32x3_weights, linear_f32x3,
-    linear_f32x3_bf16, linear_f32_raw, _transposed_weights, _LinearFn, _ZERO_BIAS, _zero_bias, linear_train, _lin, mlp, linear,
+    linear_f32x3_bf16, linear_f32_raw, _transposed_weights, _LinearFn, _SmallLinearFn, small_linear_train_ok, _ZERO_BIAS, _zero_bias, linear_train, _lin, mlp, linear,
     ffn_add_layernorm, linear_add_layernorm, patch_embed, vit_prologue_ok, vit_prologue, vit_prologue_f32_ok, vit_prologue_f32, bmm_nt_f32, score_head, add_layernorm,
     _AddLayerNormFn, add_layernorm_train_ok, add_layernorm_train,
     scale_residual_, scale_residual_layernorm_f32_, vit_f32_fused_ok, scale_residual_layernorm_, ln_fold_ok, _fold_producer_weights,
@@ -60,7 +60,7 @@ from .train import (  # noqa: F401
     _match_split, _MatchHeadFn, _match_head_domain, match_head_train_ok, match_head, nearest_partner, _CONV_FWD_PAIRS, _CONV_WGRAD_PAIRS, _conv1x1_pair_ok, _conv1x1_wgrad_ok, _Conv1x1Fn, conv1x1,
 )
 
-_SWITCHES = frozenset(['FORBID_LIBRARY_BF16_GEMM', 'GEO_TABLE', 'GEO_TABLE_F32', 'HIP_GEMM_ALL', 'PIXEL_FEATS_BF16', 'TRAIN_FUSED_SALIENCY', 'TRAIN_OWN_ATTN', 'TRAIN_OWN_CONV', 'TRAIN_OWN_GEMM', 'TRAIN_OWN_GEMM_MIN_FLOP', 'TRAIN_OWN_GEO', 'TRAIN_OWN_LINATTN', 'TRAIN_OWN_LN', 'TRAIN_OWN_MATCH', 'TRAIN_OWN_WGRAD', 'TRAIN_OWN_WGRAD_MIN_ROWS', 'USE_F32X3', 'USE_FUSED_BN_RELU', 'USE_FUSED_FINE', 'USE_FUSED_INFONCE', 'USE_FUSED_LINEAR_LN', 'USE_HIP_GEMM', 'USE_KV_VT', 'USE_LA_KV_STATE', 'USE_LN_FOLD', 'USE_OWN_TOPK', 'USE_SPARSE_UPPROJ', 'USE_STACKED_OUT', '_DIFF'])
+_SWITCHES = frozenset(['FORBID_LIBRARY_BF16_GEMM', 'GEO_TABLE', 'GEO_TABLE_F32', 'HIP_GEMM_ALL', 'PIXEL_FEATS_BF16', 'TRAIN_FUSED_SALIENCY', 'TRAIN_OWN_ATTN', 'TRAIN_OWN_CONV', 'TRAIN_OWN_GEMM', 'TRAIN_OWN_GEMM_MIN_FLOP', 'TRAIN_OWN_GEO', 'TRAIN_OWN_LINATTN', 'TRAIN_OWN_LN', 'TRAIN_OWN_MATCH', 'TRAIN_OWN_SMALL_LINEAR', 'TRAIN_OWN_WGRAD', 'TRAIN_OWN_WGRAD_MIN_ROWS', 'USE_F32X3', 'USE_FUSED_BN_RELU', 'USE_FUSED_FINE', 'USE_FUSED_INFONCE', 'USE_FUSED_LINEAR_LN', 'USE_HIP_GEMM', 'USE_KV_VT', 'USE_LA_KV_STATE', 'USE_LN_FOLD', 'USE_OWN_TOPK', 'USE_SPARSE_UPPROJ', 'USE_STACKED_OUT', '_DIFF'])
 
 
 class _OpsModule(types.ModuleType):

@@ -39,10 +39,16 @@ TRAIN_OWN_WGRAD = True  # False: the linears' weight gradients through the libra
 TRAIN_OWN_WGRAD_MIN_ROWS = 16384
 TRAIN_OWN_GEMM = True  # False: nn.Linear through the library
 # The persistent 256 x 256-tile kernels pay off from a few GFLOP per launch: below this many flops the training step keeps nn.Linear
-# (round 6 same-box A/B of the training step: 2e10 121-124 ms, 1e10 119-121, 4e9 118.2, 1e9 117-120: scripts/ubench/train_ab.py)
+# (round 6 same-box A/B of the training step: 2e10 121-124 ms, 1e10 119-121, 4e9 118.2, 1e9 117-120: scripts/ubench/train_ab.py).
+# Below the threshold an fp32 linear whose shape fits csrc/linear_small_train.hip goes to `_SmallLinearFn` when TRAIN_OWN_SMALL_LINEAR is on;
+# the rest (autocast, N = 1 heads, widths off the 64-grid, and everything while that switch is off) stays nn.Linear
 TRAIN_OWN_GEMM_MIN_FLOP = 4e9
 TRAIN_OWN_GEO = True  # round 6: the geometric embedding under autograd on the table kernels; False: the op-by-op composite
 TRAIN_OWN_ATTN = True  # the token attention core under autograd on csrc/attn_f32.hip (forward + backward kernels); False: the op-by-op composite
 TRAIN_OWN_LN = True  # residual add + LayerNorm under autograd on csrc/ln_train.hip (forward + backward kernels); False: the op-by-op composite
 TRAIN_OWN_LINATTN = True  # the focused linear attention core under autograd on csrc/linattn_train.hip (forward + backward kernels); False: the op-by-op composite
 TRAIN_OWN_MATCH = True  # the match head (InfoNCE + saliency + arg max of a block) under autograd on csrc/match_train.hip, no (B, R, C) similarity; False: the composite over the materialised matrix
+# The small fp32 linears of the 197-token layers under autograd on csrc/linear_small_train.hip (y, dX, dW + db from the tensors as stored); False:
+# nn.Linear.  Ships OFF by the rule of TRAIN_OWN_MATCH / TRAIN_OWN_LINATTN (on only if the in-process median gain exceeds the off position's own
+# spread): three same-box A/Bs gave on - off = -2.1, -1.8, -1.9 ms of 92 ms against off spreads of 0.9, 2.8, 3.4 ms (profiles/small_linear_train_ab.txt)
+TRAIN_OWN_SMALL_LINEAR = False

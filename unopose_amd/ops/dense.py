@@ -218,6 +218,74 @@ class _LinearFn(torch.autograd.Function):
         return gx, gw, gb, None, None, None
 
 
+class _SmallLinearFn(torch.autograd.Function):
+    """y = act(x W^T + b), act in {none, ReLU}, for the small fp32 linears of the matcher's 197-token layers in the training step
+    (csrc/linear_small_train.hip).  Forward, dX = (dY * act') W, and dW = (dY * act')^T X together with db = sum (dY * act') are one kernel
+    each plus one combining launch; dX and dW + db share ONE launch when both are asked for.  The kernels read x, W and dY as stored:
+    nothing derived from a weight is kept, so an in-place edit of a parameter cannot leave anything stale.  y and dX: fp32 class (bf16
+    hi / lo split in the kernel, 3 MFMAs per product); dW and db: exact fp32 products, row slices combined in double in a fixed order
+    (two runs give equal bits).  Saved: x, W, and y only with ReLU (its mask is y > 0, applied where the kernels load dY)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        N, K = weight.shape
+        x2 = _c(x)
+        w = _c(weight.detach())
+        b = None if bias is None else _c(bias.detach())
+        rows = x2.numel() // K
+        y = torch.empty(*x.shape[:-1], N, dtype=torch.float32, device=x.device)
+        with on_device(x.device):
+            call("unopose_linear_small_train_forward", ptr(x2), ptr(w), None if b is None else ptr(b), rows, N, K, int(relu), ptr(y), stream_ptr())
+        ctx.save_for_backward(x2, w, y if relu else None)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x2, w, y = ctx.saved_tensors
+        N, K = w.shape
+        rows = x2.numel() // K
+        g = _c(gy if gy.dtype == torch.float32 else gy.float())
+        if g.data_ptr() % 16:
+            g = g.clone()
+        gx = gw = gb = None
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        yp = None if y is None else ptr(y)
+        need_p = ctx.needs_input_grad[1] or need_b
+        with on_device(g.device):
+            if ctx.needs_input_grad[0]:
+                gx = torch.empty(x2.shape, dtype=torch.float32, device=g.device)
+            if need_p:
+                n_ws = lib().unopose_linear_small_train_ws_floats(rows, N, K)
+                ws = torch.empty(n_ws, dtype=torch.float32, device=g.device)
+                gw = torch.empty(N, K, dtype=torch.float32, device=g.device)
+                gb = torch.empty(N, dtype=torch.float32, device=g.device) if need_b else None
+            if gx is not None and need_p:  # dX tiles and weight-gradient slices side by side in one launch
+                call("unopose_linear_small_train_backward", ptr(g), yp, ptr(x2), ptr(w), rows, N, K, ptr(ws), n_ws, ptr(gx), ptr(gw),
+                     None if gb is None else ptr(gb), stream_ptr())
+            elif gx is not None:
+                call("unopose_linear_small_train_dx", ptr(g), yp, ptr(w), rows, N, K, ptr(gx), stream_ptr())
+            elif need_p:
+                call("unopose_linear_small_train_dwdb", ptr(g), yp, ptr(x2), rows, N, K, ptr(ws), n_ws, ptr(gw), None if gb is None else ptr(gb), stream_ptr())
+            if not ctx.needs_input_grad[1]:
+                gw = None
+        return gx, gw, gb, None
+
+
+def small_linear_train_ok(x, lin):
+    """`_SmallLinearFn` applies: switch on, CUDA, fp32 x / weight / bias outside autocast, 1 <= rows <= 16383, N and K multiples of 64 in
+    [64, 512] (the kernels' domain), 16-byte aligned once contiguous."""
+    w, b = lin.weight, lin.bias
+    if not (st.TRAIN_OWN_SMALL_LINEAR and x.is_cuda and not torch.is_autocast_enabled() and x.dtype == torch.float32 and w.dtype == torch.float32
+            and w.dim() == 2 and w.device == x.device and x.dim() >= 1):
+        return False
+    N, K = w.shape
+    if x.shape[-1] != K or N % 64 or K % 64 or not (64 <= N <= 512 and 64 <= K <= 512) or not 1 <= x.numel() // K <= 16383:
+        return False
+    return _aligned16(x) and _aligned16(w) and (b is None or (b.dtype == torch.float32 and b.device == x.device and _aligned16(b)))
+
+
 _ZERO_BIAS = {}
 
 
@@ -229,13 +297,16 @@ def _zero_bias(n, device):
 
 
 def linear_train(x, lin, relu=False):
-    """The training-mode `linear`: own GEMM forward + input gradient under autograd when the shape fits, else nn.Linear."""
+    """The training-mode `linear`: own GEMM forward + input gradient under autograd when the shape fits and pays (`_LinearFn`), the small
+    fp32 linears below that threshold on `_SmallLinearFn`, else nn.Linear."""
     N, K = lin.weight.shape
     rows = x.numel() // K
     bf16 = torch.is_autocast_enabled()
     ok = st.TRAIN_OWN_GEMM and x.is_cuda and rows > 0 and 2.0 * rows * N * K >= st.TRAIN_OWN_GEMM_MIN_FLOP and \
         (own_gemm_ok(rows, N, K) if bf16 else (x.dtype == torch.float32 and f32x3_ok(rows, N, K)))
     if not ok:
+        if small_linear_train_ok(x, lin):
+            return _SmallLinearFn.apply(x, lin.weight, lin.bias, relu)
         y = lin(x)
         return F.relu(y) if relu else y
     return _LinearFn.apply(x, lin.weight, lin.bias, lin, relu, bf16)
