@@ -1,9 +1,15 @@
 """CPU: the host half of the table-interpolated geometric embedding (ops._geo_tables) -- the tables csrc/embed.hip::geo_embed_table_kernel
 interpolates -- checked against the defining function proj(sinus(x)) of GeometricStructureEmbedding (transformer.py:303-350), with the
 kernel's own interpolation rule restated in numpy: row r holds x = (r - (NP / 2 - 1)) / 4, NP-point Lagrange on the nodes around x."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from geo_embed_ref import table_interp as _interp  # noqa: E402
 
 
 def _module():
@@ -23,22 +29,6 @@ def _exact(m, lin, x):
     om = x[:, None] * m.embedding.div_term.double().numpy()[None, :]
     s = np.stack([np.sin(om), np.cos(om)], -1).reshape(len(x), -1)
     return s @ lin.weight.detach().double().numpy().T
-
-
-def _interp(tab, x, npoint):
-    lo = npoint // 2 - 1
-    t = x * 4.0
-    r0 = np.floor(t).astype(int)
-    f = t - r0
-    out = np.zeros((len(x), tab.shape[1]))
-    nodes = np.arange(npoint) - lo
-    for j in range(npoint):
-        w = np.ones_like(f)
-        for mth in range(npoint):
-            if mth != j:
-                w *= (f - nodes[mth]) / (nodes[j] - nodes[mth])
-        out += w[:, None] * tab[r0 + j]
-    return out
 
 
 @pytest.mark.parametrize("npoint,tol", [(4, 2e-4), (6, 3e-6)])

@@ -404,6 +404,11 @@ def test_geo_embedding_under_autograd_matches_the_composite_in_float64(B, n, red
     float64: the output and the four parameter gradients, for max and mean reduction, 197 / 64 / 5 tokens."""
     import copy
 
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from geo_embed_ref import composite64
     from unopose_amd import ops
     from unopose_amd.model import UNOPose, default_model_cfg
 
@@ -424,20 +429,8 @@ def test_geo_embedding_under_autograd_matches_the_composite_in_float64(B, n, red
         p.grad = None
     # the composite in float64 (the ops of ops.geo_embedding_torch, transformer.py:303-350; neighbours from the fp32 distances like the kernel)
     p64 = pts.double()
-    dist = torch.cdist(p64, p64)
     knn = torch.cdist(pts, pts).topk(k=4, dim=2, largest=False)[1][:, :, 1:]
-    knn_pts = torch.gather(p64.unsqueeze(1).expand(B, n, n, 3), 2, knn.unsqueeze(3).expand(B, n, 3, 3))
-    rv = (knn_pts - p64.unsqueeze(2)).unsqueeze(2).expand(B, n, n, 3, 3)
-    av = (p64.unsqueeze(1) - p64.unsqueeze(2)).unsqueeze(3).expand(B, n, n, 3, 3)
-    a_idx = torch.atan2(torch.linalg.norm(torch.cross(rv, av, dim=-1), dim=-1), (rv * av).sum(-1)) * m.factor_a
-    div = m64.embedding.div_term
-
-    def sinus(idx):
-        om = idx.unsqueeze(-1) * div
-        return torch.stack([torch.sin(om), torch.cos(om)], dim=-1).reshape(*idx.shape, -1)
-
-    a_emb = m64.proj_a(sinus(a_idx))
-    ref = m64.proj_d(sinus(dist / m.sigma_d)) + (a_emb.max(dim=3)[0] if reduction == "max" else a_emb.mean(dim=3))
+    ref = composite64(p64, knn, m64, reduction)
     ref.backward(dE.double())
     # forward: the table form is fp32-class (6-point interpolation); off-diagonal entries (the diagonal's d(i,i) is rounding noise of
     # the composite's |x|^2 - 2 x.x + |x|^2, see _offdiag_err in test_model_gpu.py)

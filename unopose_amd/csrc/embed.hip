@@ -558,10 +558,10 @@ int unopose_geo_embedding(const float *points, int B, int n, const void *wd_hi, 
                           const void *wa_lo, const float *bias_sum, const float *div_term, float sigma_d,
                           float factor_a, int reduce_mean, int split, int out_bf16, int32_t *knn_ws, void *out,
                           unopose_stream_t stream) {
+  UNOPOSE_REQUIRE(B >= 0 && n >= 4 && B <= 65535, "geo_embedding: bad sizes (n must be >= 4 for 3-NN)");
+  if (B == 0) return UNOPOSE_OK;  // (before the pointer checks: the tensors of an empty batch have no storage)
   UNOPOSE_REQUIRE(points && wd_hi && wa_hi && bias_sum && div_term && knn_ws && out, "geo_embedding: null pointer");
   UNOPOSE_REQUIRE(!split || (wd_lo && wa_lo), "geo_embedding: split precision needs the lo weight parts");
-  UNOPOSE_REQUIRE(B >= 0 && n >= 4 && B <= 65535, "geo_embedding: bad sizes (n must be >= 4 for 3-NN)");
-  if (B == 0) return UNOPOSE_OK;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(geo_knn_kernel, dim3(cdiv(n, 256), B), dim3(256), 0, s, points, n, knn_ws);
   int rc = check_launch("geo_knn");
@@ -588,8 +588,8 @@ int unopose_geo_embedding(const float *points, int B, int n, const void *wd_hi, 
 int unopose_geo_embedding_table(const float *points, int B, int n, const float *tab_d, int rows_d, const float *tab_a, int rows_a,
                                 const float *bias_sum, const float *w_d, const float *div_term, int hinv, int npoint, float sigma_d, float factor_a, int reduce_mean, int out_bf16, int32_t *knn_ws,
                                 void *out, unopose_stream_t stream) {
-  UNOPOSE_REQUIRE(points && tab_d && tab_a && bias_sum && w_d && div_term && knn_ws && out, "geo_embedding_table: null pointer");
   UNOPOSE_REQUIRE(B >= 0 && n >= 4 && B <= 65535, "geo_embedding_table: bad sizes (n must be >= 4 for 3-NN)");
+  UNOPOSE_REQUIRE((B == 0 || (points && knn_ws && out)) && tab_d && tab_a && bias_sum && w_d && div_term, "geo_embedding_table: null pointer");
   UNOPOSE_REQUIRE(hinv == GT_HINV && (npoint == 4 || npoint == 6) && rows_d >= 8 && rows_a >= 8,
                   "geo_embedding_table: tables must be spaced 1 / %d (got 1 / %d) for 4- or 6-point interpolation (got %d)", GT_HINV, hinv, npoint);
   const int rdl = 16 * GT_HINV + npoint - 1;
@@ -639,8 +639,8 @@ int unopose_geo_embedding_train_workgroups(int B, int n) { return gt_train_grid(
 int unopose_geo_embedding_train_forward(const float *points, int B, int n, const float *tab_d, int rows_d, const float *tab_a, int rows_a, const float *bias_sum,
                                         const float *w_d, const float *div_term, int hinv, float sigma_d, float factor_a, int reduce_mean, int32_t *knn,
                                         float *out, void *amax, unopose_stream_t stream) {
-  UNOPOSE_REQUIRE(points && tab_d && tab_a && bias_sum && w_d && div_term && knn && out && amax, "geo_embedding_train_forward: null pointer");
   UNOPOSE_REQUIRE(B >= 0 && n >= 4 && B <= 65535, "geo_embedding_train_forward: bad sizes (n must be >= 4 for 3-NN)");
+  UNOPOSE_REQUIRE((B == 0 || (points && knn && out && amax)) && tab_d && tab_a && bias_sum && w_d && div_term, "geo_embedding_train_forward: null pointer");
   UNOPOSE_REQUIRE(hinv == GT_HINV && rows_d >= 8 && rows_a >= 8, "geo_embedding_train_forward: tables must be spaced 1 / %d (got 1 / %d)", GT_HINV, hinv);
   const int rdl = 16 * GT_HINV + 6 - 1;
   const size_t lds = ((size_t)(rows_d < rdl ? rows_d : rdl) + rows_a) * 1024;
@@ -666,7 +666,7 @@ int unopose_geo_embedding_train_forward(const float *points, int B, int n, const
 int unopose_geo_embedding_train_backward(const float *points, const int32_t *knn, int B, int n, int rows_d, int rows_a, int hinv, float sigma_d, float factor_a,
                                          int reduce_mean, const float *dE, const void *amax, float *ws, float *full_d, int *past_table,
                                          unopose_stream_t stream) {
-  UNOPOSE_REQUIRE(points && knn && dE && amax && ws && full_d && past_table, "geo_embedding_train_backward: null pointer");
+  UNOPOSE_REQUIRE((B == 0 || (points && knn && dE && amax && ws)) && full_d && past_table, "geo_embedding_train_backward: null pointer");
   UNOPOSE_REQUIRE(B >= 0 && n >= 4 && B <= 65535 && hinv == GT_HINV && rows_d >= 8 && rows_a >= 8, "geo_embedding_train_backward: bad sizes");
   const int rdl = 16 * GT_HINV + 6 - 1;
   const size_t lds = ((size_t)(rows_d < rdl ? rows_d : rdl) + rows_a) * 1024;
