@@ -10,46 +10,109 @@
 // query rows x four heads = the 16 rows of a v_mfma_f32_16x16x32_bf16 tile, so q k^T, the four per-row
 // (q W_p) E[n]^T products, the softmax (row == 16-lane DPP row) and P v all run on one set of
 // accumulators without touching HBM in between.
+#include "attn_common.h"  // (TA_NT / TA_MP, row16_max / row16_sum, zero8, wave_lds_handover)
 #include "gemm_common.h"  // (gemm_dma16: one 1-KiB LDS-DMA piece)
 
 namespace unopose {
 
-template <int XOR>
-__device__ __forceinline__ float swz_xor(float v) {  // butterfly step inside a 16-lane row, no LDS memory touched
-  // (DPP rather than ds_swizzle through the LDS crossbar: DESIGN.md section 7)
-  // DPP: quad_perm [1,0,3,2] / [2,3,0,1] for xor 1 / 2; row_half_mirror / row_mirror for xor 4 / 8 -- applied in this order every
-  // lane's partner group holds the value the xor partner would (the groups are uniform by then), so sums and maxima are unchanged
-  constexpr int ctrl = XOR == 1 ? 0xB1 : XOR == 2 ? 0x4E : XOR == 4 ? 0x141 : 0x140;
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float row16_max(float v) {
-  v = fmaxf(v, swz_xor<1>(v));
-  v = fmaxf(v, swz_xor<2>(v));
-  v = fmaxf(v, swz_xor<4>(v));
-  v = fmaxf(v, swz_xor<8>(v));
-  return v;
-}
-__device__ __forceinline__ float row16_sum(float v) {
-  v += swz_xor<1>(v);
-  v += swz_xor<2>(v);
-  v += swz_xor<4>(v);
-  v += swz_xor<8>(v);
-  return v;
-}
+// ---- The three stages both kernels run on one set of accumulators.  li = lane & 15, kg = lane >> 4: A operand row li, k-group kg |
+// B operand column li, k-group kg | C/D row kg * 4 + reg = (query row kg, head reg), column li.
 
-__device__ __forceinline__ bf16x8 zero8() {
-  bf16x8 z;
+// q k^T: block-diagonal A (row (n_l,h) = li only sees head h's 64 channels of its query row Q), B = K.
+// K is L2-resident but every fragment load still costs an L2 round trip: the 14 key-tile loads of
+// k-step ks+1 are all issued before the 14 MFMAs of k-step ks (double-buffered), not one by one.
+__device__ __forceinline__ void token_attn_qk(const u16 *Q, bool a_valid, int a_h, const u16 *K, int ldk, int m, int li, int kg,
+                                              f32x4 (&acc)[TA_NT]) {
+  bf16x8 qa[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) z[i] = (__bf16)0.f;
-  return z;
+  for (int ks = 0; ks < 8; ++ks) {
+    const int kk = ks * 32 + kg * 8;
+    qa[ks] = zero8();
+    if (a_valid && (kk >> 6) == a_h) qa[ks] = *reinterpret_cast<const bf16x8 *>(Q + kk);
+  }
+  bf16x8 kb[2][TA_NT];
+  auto load_k = [&](int ks, bf16x8 (&dst)[TA_NT]) {
+#pragma unroll
+    for (int t = 0; t < TA_NT; ++t) {
+      // keys >= m read the last key's row instead of branching per load: their scores are masked in the softmax
+      const int mm = min(t * 16 + li, m - 1);
+      dst[t] = *reinterpret_cast<const bf16x8 *>(K + (size_t)mm * ldk + ks * 32 + kg * 8);
+    }
+  };
+  load_k(0, kb[0]);
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) {
+    if (ks + 1 < 8) load_k(ks + 1, kb[(ks + 1) & 1]);
+#pragma unroll
+    for (int t = 0; t < TA_NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[ks], kb[ks & 1][t], acc[t], 0, 0, 0);
+  }
 }
 
-constexpr int TA_NT = 14;          // key tiles of 16 -> up to 224 keys
-constexpr int TA_MP = TA_NT * 16;  // padded key count (V^T and the P staging use this stride)
+// softmax over keys (keys >= m masked): leaves the unnormalised p in acc and 1 / row sum in sm
+__device__ __forceinline__ void token_attn_softmax(f32x4 (&acc)[TA_NT], float (&sm)[4], int m, float scale, int li) {
+  float mx[4] = {-3e38f, -3e38f, -3e38f, -3e38f};
+#pragma unroll
+  for (int t = 0; t < TA_NT; ++t) {
+    const bool ok = t * 16 + li < m;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      acc[t][h] = ok ? acc[t][h] * scale : -3e38f;
+      mx[h] = fmaxf(mx[h], acc[t][h]);
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    mx[h] = row16_max(mx[h]);
+    sm[h] = 0.f;
+  }
+#pragma unroll
+  for (int t = 0; t < TA_NT; ++t) {
+    const bool ok = t * 16 + li < m;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      const float p = ok ? __expf(acc[t][h] - mx[h]) : 0.f;
+      acc[t][h] = p;
+      sm[h] += p;
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 4; ++h) sm[h] = 1.f / row16_sum(sm[h]);
+}
 
-// RW = query rows per wavefront (4 fills the 16-row MFMA tile; 2 doubles the number of wavefronts that
-// stream E concurrently -- the kernel is bound by HBM latency x occupancy, not by the matrix pipe)
-template <bool RPE, int RW>
+// P v.  P (bf16) goes through the wave's 16 LDS rows Pl into A-operand order: row (query row, head), column key.  B = V^T (VT: this
+// cloud's, channel-major, zero-padded keys); only the head-matching quarter is kept.  This lane's query row n0 + kg starts at out_row
+// and is stored where row_ok.
+__device__ __forceinline__ void token_attn_pv(const f32x4 (&acc)[TA_NT], const float (&sm)[4], u16 (*Pl)[TA_MP], const u16 *VT, int li,
+                                              int kg, bool row_ok, u16 *out_row) {
+#pragma unroll
+  for (int t = 0; t < TA_NT; ++t)
+#pragma unroll
+    for (int h = 0; h < 4; ++h) Pl[kg * 4 + h][t * 16 + li] = f2bf(acc[t][h] * sm[h]);
+  wave_lds_handover();
+  constexpr int PK = TA_MP / 32;
+  bf16x8 pa[PK];
+#pragma unroll
+  for (int ks = 0; ks < PK; ++ks) pa[ks] = *reinterpret_cast<const bf16x8 *>(&Pl[li][ks * 32 + kg * 8]);
+  bf16x8 vb[2][PK];
+  auto load_v = [&](int nt, bf16x8 (&dst)[PK]) {
+    const u16 *Vr = VT + (size_t)(nt * 16 + li) * TA_MP + kg * 8;
+#pragma unroll
+    for (int ks = 0; ks < PK; ++ks) dst[ks] = *reinterpret_cast<const bf16x8 *>(Vr + ks * 32);
+  };
+  load_v(0, vb[0]);
+#pragma unroll
+  for (int nt = 0; nt < 16; ++nt) {
+    if (nt + 1 < 16) load_v(nt + 1, vb[(nt + 1) & 1]);  // next channel tile's V^T fragments in flight
+    f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < PK; ++ks) o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[ks], vb[nt & 1][ks], o, 0, 0, 0);
+    // D row = (query row kg, head reg); channel tile nt belongs to head nt >> 2
+    if (row_ok) out_row[nt * 16 + li] = f2bf(o[nt >> 2]);
+  }
+}
+
+// One wave = 4 query rows (they fill the 16-row MFMA tile with the 4 heads); E, if any, by fragment loads from global memory.
+template <bool RPE>
 __global__ __launch_bounds__(256, 2) void token_attn_kernel(const u16 *__restrict__ q, int ldq,
                                                          const u16 *__restrict__ k, int ldk,
                                                          const u16 *__restrict__ vt, const u16 *__restrict__ qp,
@@ -58,49 +121,18 @@ __global__ __launch_bounds__(256, 2) void token_attn_kernel(const u16 *__restric
   __shared__ __attribute__((aligned(16))) u16 Pl[4][16][TA_MP];
   __shared__ __attribute__((aligned(16))) u16 Al[RPE ? 4 : 1][8][64][8];  // RPE: A fragments of the current query row
   const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n0 = (blockIdx.x * 4 + wave) * RW;  // first of this wave's RW query rows
+  const int n0 = (blockIdx.x * 4 + wave) * 4;  // first of this wave's 4 query rows
   if (n0 >= n) return;
-  const int li = lane & 15, kg = lane >> 4;     // A: row li, k-group kg | B: column li, k-group kg
+  const int li = lane & 15, kg = lane >> 4;
   const int a_nl = li >> 2, a_h = li & 3;       // A-operand row = (query row a_nl, head a_h)
-  const bool a_valid = a_nl < RW && n0 + a_nl < n;
-  const u16 *Q = q + ((size_t)b * n + n0 + a_nl) * ldq;
-  const u16 *K = k + (size_t)b * m * ldk;
 
   f32x4 acc[TA_NT];
 #pragma unroll
   for (int t = 0; t < TA_NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // ---- q k^T: block-diagonal A (row (n_l,h) only sees head h's 64 channels), B = K.
-  // K is L2-resident but every fragment load still costs an L2 round trip: the 14 key-tile loads of
-  // k-step ks+1 are all issued before the 14 MFMAs of k-step ks (double-buffered), not one by one.
-  {
-    bf16x8 qa[8];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      const int kk = ks * 32 + kg * 8;
-      qa[ks] = zero8();
-      if (a_valid && (kk >> 6) == a_h) qa[ks] = *reinterpret_cast<const bf16x8 *>(Q + kk);
-    }
-    bf16x8 kb[2][TA_NT];
-    auto load_k = [&](int ks, bf16x8 (&dst)[TA_NT]) {
-#pragma unroll
-      for (int t = 0; t < TA_NT; ++t) {
-        // keys >= m read the last key's row instead of branching per load: their scores are masked below
-        const int mm = min(t * 16 + li, m - 1);
-        dst[t] = *reinterpret_cast<const bf16x8 *>(K + (size_t)mm * ldk + ks * 32 + kg * 8);
-      }
-    };
-    load_k(0, kb[0]);
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      if (ks + 1 < 8) load_k(ks + 1, kb[(ks + 1) & 1]);
-#pragma unroll
-      for (int t = 0; t < TA_NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[ks], kb[ks & 1][t], acc[t], 0, 0, 0);
-    }
-  }
+  token_attn_qk(q + ((size_t)b * n + n0 + a_nl) * ldq, n0 + a_nl < n, a_h, k + (size_t)b * m * ldk, ldk, m, li, kg, acc);
   // ---- RPE term: for each of the 4 query rows, (q W_p)[n] . E[n,m,:]
   if (RPE) {
-    for (int nl = 0; nl < RW; ++nl) {
+    for (int nl = 0; nl < 4; ++nl) {
       if (n0 + nl >= n) break;  // wave-uniform
       const u16 *QP = qp + ((size_t)b * n + n0 + nl) * ldqp + a_h * 256;
       const u16 *En = E + ((size_t)b * n + n0 + nl) * (size_t)m * 256;
@@ -136,66 +168,9 @@ __global__ __launch_bounds__(256, 2) void token_attn_kernel(const u16 *__restric
       }
     }
   }
-  // ---- softmax over keys: C/D layout row = kg*4 + reg = (query row kg, head reg), column = key li
-  float mx[4] = {-3e38f, -3e38f, -3e38f, -3e38f};
-#pragma unroll
-  for (int t = 0; t < TA_NT; ++t) {
-    const bool ok = t * 16 + li < m;
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      acc[t][h] = ok ? acc[t][h] * scale : -3e38f;
-      mx[h] = fmaxf(mx[h], acc[t][h]);
-    }
-  }
   float sm[4];
-#pragma unroll
-  for (int h = 0; h < 4; ++h) {
-    mx[h] = row16_max(mx[h]);
-    sm[h] = 0.f;
-  }
-#pragma unroll
-  for (int t = 0; t < TA_NT; ++t) {
-    const bool ok = t * 16 + li < m;
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      const float p = ok ? __expf(acc[t][h] - mx[h]) : 0.f;
-      acc[t][h] = p;
-      sm[h] += p;
-    }
-  }
-#pragma unroll
-  for (int h = 0; h < 4; ++h) sm[h] = 1.f / row16_sum(sm[h]);
-  // ---- P (bf16) -> LDS in A-operand order: row (query row, head), column key
-#pragma unroll
-  for (int t = 0; t < TA_NT; ++t)
-#pragma unroll
-    for (int h = 0; h < 4; ++h) Pl[wave][kg * 4 + h][t * 16 + li] = f2bf(acc[t][h] * sm[h]);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  // ---- P v: B = V^T (channel-major, zero-padded keys); only the head-matching quarter is kept
-  bf16x8 pa[TA_MP / 32];
-#pragma unroll
-  for (int ks = 0; ks < TA_MP / 32; ++ks)
-    pa[ks] = *reinterpret_cast<const bf16x8 *>(&Pl[wave][li][ks * 32 + kg * 8]);
-  const u16 *VT = vt + (size_t)b * 256 * TA_MP;
-  constexpr int PK = TA_MP / 32;
-  bf16x8 vb[2][PK];
-  auto load_v = [&](int nt, bf16x8 (&dst)[PK]) {
-    const u16 *Vr = VT + (size_t)(nt * 16 + li) * TA_MP + kg * 8;
-#pragma unroll
-    for (int ks = 0; ks < PK; ++ks) dst[ks] = *reinterpret_cast<const bf16x8 *>(Vr + ks * 32);
-  };
-  load_v(0, vb[0]);
-#pragma unroll
-  for (int nt = 0; nt < 16; ++nt) {
-    if (nt + 1 < 16) load_v(nt + 1, vb[(nt + 1) & 1]);  // next channel tile's V^T fragments in flight
-    f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < PK; ++ks) o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[ks], vb[nt & 1][ks], o, 0, 0, 0);
-    // D row = (query row kg, head reg); channel tile nt belongs to head nt >> 2
-    if (kg < RW && n0 + kg < n) out[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = f2bf(o[nt >> 2]);
-  }
+  token_attn_softmax(acc, sm, m, scale, li);
+  token_attn_pv(acc, sm, Pl[wave], vt + (size_t)b * 256 * TA_MP, li, kg, n0 + kg < n, out + ((size_t)b * n + n0 + kg) * 256);
 }
 
 // ---- Round 5: the RPE self-attention with the embedding stream staged through LDS by LDS-DMA.
@@ -230,8 +205,6 @@ __global__ __launch_bounds__(256, 2) void token_attn_rpe_dma_kernel(const u16 *_
   for (int n0 = nbase; n0 < min(n, nbase + TA_ROWS); n0 += RW) {
   const int rw_here = min(RW, min(n, nbase + TA_ROWS) - n0);
   const bool a_valid = a_nl < rw_here;
-  const u16 *Q = q + ((size_t)b * n + n0 + a_nl) * ldq;
-  const u16 *K = k + (size_t)b * m * ldk;
 
   f32x4 acc[TA_NT];
 #pragma unroll
@@ -272,31 +245,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_rpe_dma_kernel(const u16 *_
       if (a_valid) myq[ks] = *reinterpret_cast<const bf16x8 *>(QP + ks * 32 + kg * 8);
     }
   }
-  // ---- q k^T (as token_attn_kernel)
-  {
-    bf16x8 qa[8];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      const int kk = ks * 32 + kg * 8;
-      qa[ks] = zero8();
-      if (a_valid && (kk >> 6) == a_h) qa[ks] = *reinterpret_cast<const bf16x8 *>(Q + kk);
-    }
-    bf16x8 kb[2][TA_NT];
-    auto load_k = [&](int ks, bf16x8 (&dst)[TA_NT]) {
-#pragma unroll
-      for (int t = 0; t < TA_NT; ++t) {
-        const int mm = min(t * 16 + li, m - 1);
-        dst[t] = *reinterpret_cast<const bf16x8 *>(K + (size_t)mm * ldk + ks * 32 + kg * 8);
-      }
-    };
-    load_k(0, kb[0]);
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      if (ks + 1 < 8) load_k(ks + 1, kb[(ks + 1) & 1]);
-#pragma unroll
-      for (int t = 0; t < TA_NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[ks], kb[ks & 1][t], acc[t], 0, 0, 0);
-    }
-  }
+  token_attn_qk(q + ((size_t)b * n + n0 + a_nl) * ldq, a_valid, a_h, k + (size_t)b * m * ldk, ldk, m, li, kg, acc);
   // (the compiler's own waits for the plain loads above have drained the first two tiles as well: from here on the counted waits rule)
   // ---- RPE term
   const char *ringw = &ring[0][0] + wave * TA_RING;
@@ -327,64 +276,11 @@ __global__ __launch_bounds__(256, 2) void token_attn_rpe_dma_kernel(const u16 *_
       ++s;
     }
   }
-  // ---- softmax over keys: C/D layout row = kg*4 + reg = (query row kg, head reg), column = key li
-  float mx[4] = {-3e38f, -3e38f, -3e38f, -3e38f};
-#pragma unroll
-  for (int t = 0; t < TA_NT; ++t) {
-    const bool ok = t * 16 + li < m;
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      acc[t][h] = ok ? acc[t][h] * scale : -3e38f;
-      mx[h] = fmaxf(mx[h], acc[t][h]);
-    }
-  }
   float sm[4];
-#pragma unroll
-  for (int h = 0; h < 4; ++h) {
-    mx[h] = row16_max(mx[h]);
-    sm[h] = 0.f;
-  }
-#pragma unroll
-  for (int t = 0; t < TA_NT; ++t) {
-    const bool ok = t * 16 + li < m;
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      const float p = ok ? __expf(acc[t][h] - mx[h]) : 0.f;
-      acc[t][h] = p;
-      sm[h] += p;
-    }
-  }
-#pragma unroll
-  for (int h = 0; h < 4; ++h) sm[h] = 1.f / row16_sum(sm[h]);
-  // ---- P (bf16) -> LDS in A-operand order (the wave's own ring space: the stream has ended, every tile has been read)
-  u16(*Pl)[TA_MP] = reinterpret_cast<u16(*)[TA_MP]>(const_cast<char *>(ringw));
-#pragma unroll
-  for (int t = 0; t < TA_NT; ++t)
-#pragma unroll
-    for (int h = 0; h < 4; ++h) Pl[kg * 4 + h][t * 16 + li] = f2bf(acc[t][h] * sm[h]);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  bf16x8 pa[TA_MP / 32];
-#pragma unroll
-  for (int ks = 0; ks < TA_MP / 32; ++ks) pa[ks] = *reinterpret_cast<const bf16x8 *>(&Pl[li][ks * 32 + kg * 8]);
-  const u16 *VT = vt + (size_t)b * 256 * TA_MP;
-  constexpr int PK = TA_MP / 32;
-  bf16x8 vb[2][PK];
-  auto load_v = [&](int nt, bf16x8 (&dst)[PK]) {
-    const u16 *Vr = VT + (size_t)(nt * 16 + li) * TA_MP + kg * 8;
-#pragma unroll
-    for (int ks = 0; ks < PK; ++ks) dst[ks] = *reinterpret_cast<const bf16x8 *>(Vr + ks * 32);
-  };
-  load_v(0, vb[0]);
-#pragma unroll
-  for (int nt = 0; nt < 16; ++nt) {
-    if (nt + 1 < 16) load_v(nt + 1, vb[(nt + 1) & 1]);
-    f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < PK; ++ks) o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[ks], vb[nt & 1][ks], o, 0, 0, 0);
-    if (kg < rw_here) out[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = f2bf(o[nt >> 2]);
-  }
+  token_attn_softmax(acc, sm, m, scale, li);
+  // P staging in the wave's own ring space: the stream has ended, every tile has been read
+  token_attn_pv(acc, sm, reinterpret_cast<u16(*)[TA_MP]>(const_cast<char *>(ringw)), vt + (size_t)b * 256 * TA_MP, li, kg, kg < rw_here,
+                out + ((size_t)b * n + n0 + kg) * 256);
   // (the P staging above reused the ring: every lane's reads of it are done before the next tile's stream is started)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }  // row tiles of the wave
@@ -413,11 +309,11 @@ int unopose_token_attention(const void *q, int ldq, const void *k, int ldk, cons
     hipLaunchKernelGGL(token_attn_rpe_dma_kernel, dim3(cdiv(n, 4 * TA_ROWS), B), dim3(256), 0, s, (const u16 *)q, ldq, (const u16 *)k, ldk, (const u16 *)vt,
                        (const u16 *)qp, ldqp, (const u16 *)E, n, m, scale, B, (u16 *)out);
   } else if (E)
-    hipLaunchKernelGGL((token_attn_kernel<true, 4>), dim3(cdiv(n, 16), B), dim3(256), 0, s, (const u16 *)q,
+    hipLaunchKernelGGL((token_attn_kernel<true>), dim3(cdiv(n, 16), B), dim3(256), 0, s, (const u16 *)q,
                        ldq, (const u16 *)k, ldk, (const u16 *)vt, (const u16 *)qp, ldqp, (const u16 *)E, n, m, scale,
                        (u16 *)out);
   else
-    hipLaunchKernelGGL((token_attn_kernel<false, 4>), dim3(cdiv(n, 16), B), dim3(256), 0, s, (const u16 *)q,
+    hipLaunchKernelGGL((token_attn_kernel<false>), dim3(cdiv(n, 16), B), dim3(256), 0, s, (const u16 *)q,
                        ldq, (const u16 *)k, ldk, (const u16 *)vt, (const u16 *)nullptr, 0, (const u16 *)nullptr, n, m,
                        scale, (u16 *)out);
   return check_launch("token_attention");

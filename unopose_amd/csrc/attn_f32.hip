@@ -6,7 +6,7 @@
 // exact fp32 MFMA runs at 1/16 of the bf16 rate; instead every operand is split on the fly into
 // hi + lo bfloat16 parts and each product is issued as 3 bf16 MFMAs (a_hi b_hi + a_hi b_lo + a_lo b_hi,
 // fp32 accumulation): ~2^-16 relative error per product, i.e. fp32-class results at 5x the fp32 MFMA rate.
-#include "common.h"
+#include "attn_common.h"  // (TA_NT / TA_MP, row16_sum / row16_max, zero8, wave_lds_handover)
 
 namespace unopose {
 
@@ -15,21 +15,76 @@ __device__ __forceinline__ bf16x8_hl af_load8(const float *p) {  // 8 consecutiv
   const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
   return split8_bf16(v);
 }
-__device__ __forceinline__ bf16x8_hl af_zero() {
-  float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  return split8_bf16(z);
-}
+__device__ __forceinline__ bf16x8_hl af_zero() { return bf16x8_hl{zero8(), zero8()}; }
 
-template <int XOR>
-__device__ __forceinline__ float af_swz(float v) {
-  return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (XOR << 10) | 0x1F));
-}
-
-constexpr int AF_NT = 14, AF_MP = AF_NT * 16;
+// ---- The two MFMA loops of the token attention, forward and backward.  Operand streams straight from global memory (K is L2-resident,
+// the geometric embedding E is a 2.5 GB HBM stream per launch): the raw 32-byte pieces of the next AF_PF_DEPTH operand pairs are in
+// flight while the current one is split and multiplied -- the compiler had issued every pair of loads directly in front of its three
+// MFMAs (one exposed memory round trip per 3 MFMAs).
 constexpr int AF_PF_DEPTH = 4;  // operand pairs in flight ahead of the MFMAs of the token attention
+struct AfRaw {
+  float4 a, b;
+};
+__device__ __forceinline__ AfRaw af_ld8(const float *p) {
+  return AfRaw{*reinterpret_cast<const float4 *>(p), *reinterpret_cast<const float4 *>(p + 4)};
+}
+__device__ __forceinline__ bf16x8_hl af_sp8(const AfRaw &r) {
+  const float v[8] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w};
+  return split8_bf16(v);
+}
+
+// A fragment of k-step ks of a block-diagonal A operand: row li = (query row, head a_h) of A_row only sees head a_h's 64 channels
+__device__ __forceinline__ bf16x8_hl af_head_frag(const float *A_row, bool a_valid, int a_h, int kg, int ks) {
+  const int kk = ks * 32 + kg * 8;
+  bf16x8_hl a = af_zero();
+  if (a_valid && (kk >> 6) == a_h) a = af_load8(A_row + kk);
+  return a;
+}
+
+// acc[t] += A B^T over the 8 k-steps x TA_NT key tiles, k-step outermost.  a_frag(ks): this lane's A fragment of k-step ks, asked for
+// once per k-step and in order; B_rows: m rows of 256 channels with stride ldb (rows >= m read row m - 1: masked by the caller).
+template <class AFrag>
+__device__ __forceinline__ void af_scores(AFrag a_frag, const float *B_rows, size_t ldb, int m, int nt_valid, int li, int kg,
+                                          f32x4 (&acc)[TA_NT]) {
+  constexpr int NPAIR = 8 * TA_NT;
+  auto addr = [&](int i) { return B_rows + (size_t)min((i % TA_NT) * 16 + li, m - 1) * ldb + (i / TA_NT) * 32 + kg * 8; };
+  AfRaw ring[AF_PF_DEPTH];
+#pragma unroll
+  for (int i = 0; i < AF_PF_DEPTH; ++i) ring[i] = af_ld8(addr(i));
+  bf16x8_hl a = af_zero();
+#pragma unroll
+  for (int i = 0; i < NPAIR; ++i) {
+    const int ks = i / TA_NT, t = i % TA_NT;
+    if (t == 0) a = a_frag(ks);
+    const AfRaw cur = ring[i % AF_PF_DEPTH];
+    if (i + AF_PF_DEPTH < NPAIR) ring[i % AF_PF_DEPTH] = af_ld8(addr(i + AF_PF_DEPTH));
+    if (t < nt_valid) acc[t] = mfma3_hh_hl_lh_16x16(a, af_sp8(cur), acc[t]);
+  }
+}
+
+// emit(nt, o) for the 16 channel tiles nt of frags . BT, where BT (256, TA_MP) is the channel-major, zero-padded B^T of this cloud and
+// o the value of row (query row kg, head nt >> 2), channel nt * 16 + li: only the head-matching quarter of the D tile is kept.
+template <class Emit>
+__device__ __forceinline__ void af_apply(const bf16x8_hl (&frags)[TA_MP / 32], const float *BT, int li, int kg, Emit emit) {
+  constexpr int NKS = TA_MP / 32, NP2 = 16 * NKS;
+  auto addr = [&](int i) { return BT + (size_t)((i / NKS) * 16 + li) * TA_MP + kg * 8 + (i % NKS) * 32; };
+  AfRaw ring[AF_PF_DEPTH];
+#pragma unroll
+  for (int i = 0; i < AF_PF_DEPTH; ++i) ring[i] = af_ld8(addr(i));
+  f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < NP2; ++i) {
+    const int nt = i / NKS, ks = i % NKS;
+    if (ks == 0) o = f32x4{0.f, 0.f, 0.f, 0.f};
+    const AfRaw cur = ring[i % AF_PF_DEPTH];
+    if (i + AF_PF_DEPTH < NP2) ring[i % AF_PF_DEPTH] = af_ld8(addr(i + AF_PF_DEPTH));
+    o = mfma3_hh_hl_lh_16x16(frags[ks], af_sp8(cur), o);
+    if (ks == NKS - 1) emit(nt, o[nt >> 2]);
+  }
+}
 
 // ---- token attention (see attn.hip for the scheme): one wave = 4 query rows x 4 heads ----------------
-// STORE_P (training forward): P is also written to pst (B,4,n,AF_MP), zero on the padded keys, for the backward below.
+// STORE_P (training forward): P is also written to pst (B,4,n,TA_MP), zero on the padded keys, for the backward below.
 template <bool RPE, bool STORE_P = false>
 __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__restrict__ q, int ldq,
                                                              const float *__restrict__ k, int ldk,
@@ -37,7 +92,7 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
                                                              const float *__restrict__ qp, int ldqp,
                                                              const float *__restrict__ E, int n, int m, float scale,
                                                              float *__restrict__ out, float *__restrict__ pst) {
-  __shared__ __attribute__((aligned(16))) float Pl[4][16][AF_MP + 4];
+  __shared__ __attribute__((aligned(16))) float Pl[4][16][TA_MP + 4];
   const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n0 = (blockIdx.x * 4 + wave) * 4;
   if (n0 >= n) return;
@@ -46,75 +101,28 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
   const bool a_valid = n0 + a_nl < n;
   const float *Q = q + ((size_t)b * n + n0 + a_nl) * ldq;
   const float *K = k + (size_t)b * m * ldk;
-  f32x4 acc[AF_NT];
+  f32x4 acc[TA_NT];
 #pragma unroll
-  for (int t = 0; t < AF_NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < TA_NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nt_valid = (m + 15) >> 4;
-  // Operand streams straight from global memory (K is L2-resident, the geometric embedding E is a 2.5 GB HBM stream per launch): the
-  // raw 32-byte pieces of the next AF_PF (k-step, key tile) pairs are in flight while the current one is split and multiplied -- the
-  // compiler had issued every pair of loads directly in front of its three MFMAs (one exposed memory round trip per 3 MFMAs).
-  struct Raw {
-    float4 a, b;
-  };
-  auto ld8 = [](const float *p) { return Raw{*reinterpret_cast<const float4 *>(p), *reinterpret_cast<const float4 *>(p + 4)}; };
-  auto sp8 = [](const Raw &r) {
-    const float v[8] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w};
-    return split8_bf16(v);
-  };
-  constexpr int AF_PF = AF_PF_DEPTH, NPAIR = 8 * AF_NT;
-  {
-    auto addr = [&](int i) { return K + (size_t)min((i % AF_NT) * 16 + li, m - 1) * ldk + (i / AF_NT) * 32 + kg * 8; };
-    Raw ring[AF_PF];
-#pragma unroll
-    for (int i = 0; i < AF_PF; ++i) ring[i] = ld8(addr(i));
-    bf16x8_hl a = af_zero();
-#pragma unroll
-    for (int i = 0; i < NPAIR; ++i) {
-      const int ks = i / AF_NT, t = i % AF_NT;
-      if (t == 0) {
-        const int kk = ks * 32 + kg * 8;
-        a = af_zero();
-        if (a_valid && (kk >> 6) == a_h) a = af_load8(Q + kk);
-      }
-      const Raw cur = ring[i % AF_PF];
-      if (i + AF_PF < NPAIR) ring[i % AF_PF] = ld8(addr(i + AF_PF));
-      if (t < nt_valid) {
-        const bf16x8_hl bv = sp8(cur);
-        acc[t] = mfma3_hh_hl_lh_16x16(a, bv, acc[t]);
-      }
-    }
-  }
+  af_scores([&](int ks) { return af_head_frag(Q, a_valid, a_h, kg, ks); }, K, ldk, m, nt_valid, li, kg, acc);
   if (RPE) {
     for (int nl = 0; nl < 4; ++nl) {
       if (n0 + nl >= n) break;
       const float *QP = qp + ((size_t)b * n + n0 + nl) * ldqp + a_h * 256;
-      const float *En = E + ((size_t)b * n + n0 + nl) * (size_t)m * 256;
-      auto addr = [&](int i) { return En + (size_t)min((i % AF_NT) * 16 + li, m - 1) * 256 + (i / AF_NT) * 32 + kg * 8; };
-      Raw ring[AF_PF];
-#pragma unroll
-      for (int i = 0; i < AF_PF; ++i) ring[i] = ld8(addr(i));
-      Raw araw = ld8(QP + kg * 8);  // the query-side fragment of k-step 0; the next one is fetched a whole k-step ahead
-      bf16x8_hl a = af_zero();
-#pragma unroll
-      for (int i = 0; i < NPAIR; ++i) {
-        const int ks = i / AF_NT, t = i % AF_NT;
-        if (t == 0) {
-          a = af_zero();
-          if (a_nl == nl) a = sp8(araw);
-          if (ks + 1 < 8) araw = ld8(QP + (ks + 1) * 32 + kg * 8);
-        }
-        const Raw cur = ring[i % AF_PF];
-        if (i + AF_PF < NPAIR) ring[i % AF_PF] = ld8(addr(i + AF_PF));
-        if (t < nt_valid) {
-          const bf16x8_hl bv = sp8(cur);
-          acc[t] = mfma3_hh_hl_lh_16x16(a, bv, acc[t]);
-        }
-      }
+      AfRaw araw = af_ld8(QP + kg * 8);  // the query-side fragment of k-step 0; the next one is fetched a whole k-step ahead
+      auto a_frag = [&](int ks) {
+        bf16x8_hl a = af_zero();
+        if (a_nl == nl) a = af_sp8(araw);
+        if (ks + 1 < 8) araw = af_ld8(QP + (ks + 1) * 32 + kg * 8);
+        return a;
+      };
+      af_scores(a_frag, E + ((size_t)b * n + n0 + nl) * (size_t)m * 256, 256, m, nt_valid, li, kg, acc);
     }
   }
   float mx[4] = {-3e38f, -3e38f, -3e38f, -3e38f};
 #pragma unroll
-  for (int t = 0; t < AF_NT; ++t) {
+  for (int t = 0; t < TA_NT; ++t) {
     const bool ok = t * 16 + li < m;
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
@@ -125,13 +133,11 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
   float sm[4];
 #pragma unroll
   for (int h = 0; h < 4; ++h) {
-    float v = mx[h];
-    v = fmaxf(v, af_swz<1>(v)); v = fmaxf(v, af_swz<2>(v)); v = fmaxf(v, af_swz<4>(v)); v = fmaxf(v, af_swz<8>(v));
-    mx[h] = v;
+    mx[h] = row16_max(mx[h]);
     sm[h] = 0.f;
   }
 #pragma unroll
-  for (int t = 0; t < AF_NT; ++t) {
+  for (int t = 0; t < TA_NT; ++t) {
     const bool ok = t * 16 + li < m;
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
@@ -141,47 +147,25 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
     }
   }
 #pragma unroll
-  for (int h = 0; h < 4; ++h) {
-    float v = sm[h];
-    v += af_swz<1>(v); v += af_swz<2>(v); v += af_swz<4>(v); v += af_swz<8>(v);
-    sm[h] = 1.f / v;
-  }
+  for (int h = 0; h < 4; ++h) sm[h] = 1.f / row16_sum(sm[h]);
 #pragma unroll
-  for (int t = 0; t < AF_NT; ++t)
+  for (int t = 0; t < TA_NT; ++t)
 #pragma unroll
     for (int h = 0; h < 4; ++h) Pl[wave][kg * 4 + h][t * 16 + li] = acc[t][h] * sm[h];
   if (STORE_P && n0 + kg < n) {
-    float *Pr = pst + ((size_t)b * 4 * n + n0 + kg) * AF_MP + li;
+    float *Pr = pst + ((size_t)b * 4 * n + n0 + kg) * TA_MP + li;
 #pragma unroll
-    for (int t = 0; t < AF_NT; ++t)
+    for (int t = 0; t < TA_NT; ++t)
 #pragma unroll
-      for (int h = 0; h < 4; ++h) Pr[(size_t)h * n * AF_MP + t * 16] = acc[t][h] * sm[h];
+      for (int h = 0; h < 4; ++h) Pr[(size_t)h * n * TA_MP + t * 16] = acc[t][h] * sm[h];
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  bf16x8_hl pa[AF_MP / 32];
+  wave_lds_handover();
+  bf16x8_hl pa[TA_MP / 32];
 #pragma unroll
-  for (int ks = 0; ks < AF_MP / 32; ++ks) pa[ks] = af_load8(&Pl[wave][li][ks * 32 + kg * 8]);
-  const float *VT = vt + (size_t)b * 256 * AF_MP;
-  {
-    constexpr int NKS = AF_MP / 32, NP2 = 16 * NKS;
-    auto addr = [&](int i) { return VT + (size_t)((i / NKS) * 16 + li) * AF_MP + kg * 8 + (i % NKS) * 32; };
-    Raw ring[AF_PF];
-#pragma unroll
-    for (int i = 0; i < AF_PF; ++i) ring[i] = ld8(addr(i));
-    f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < NP2; ++i) {
-      const int nt = i / NKS, ks = i % NKS;
-      if (ks == 0) o = f32x4{0.f, 0.f, 0.f, 0.f};
-      const Raw cur = ring[i % AF_PF];
-      if (i + AF_PF < NP2) ring[i % AF_PF] = ld8(addr(i + AF_PF));
-      const bf16x8_hl bv = sp8(cur);
-      o = mfma3_hh_hl_lh_16x16(pa[ks], bv, o);
-      if (ks == NKS - 1 && n0 + kg < n) out[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = o[nt >> 2];
-    }
-  }
+  for (int ks = 0; ks < TA_MP / 32; ++ks) pa[ks] = af_load8(&Pl[wave][li][ks * 32 + kg * 8]);
+  af_apply(pa, vt + (size_t)b * 256 * TA_MP, li, kg, [&](int nt, float o) {
+    if (n0 + kg < n) out[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = o;
+  });
 }
 
 // ---- token attention backward (training): S = scale (q k^T [+ qp . E]), P = softmax(S), O = P v; given dO:
@@ -190,12 +174,12 @@ __global__ __launch_bounds__(256) void token_attn_f32_kernel(const float *__rest
 // Three kernels, each output element owned by one thread (no atomics): dq + dS (the forward's scheme: hi / lo-split MFMAs), the RPE terms
 // (E streamed once, dE written once; exact fp32 FMA: 8 per element of E, far under the memory time) and dk / dv (fp32 FMA, LDS tiles).
 
-// One wave = 4 query rows x 4 heads, as in the forward.  P: the forward's (B,4,n,AF_MP) (zero on padded keys, so dS is too);
-// kt (B,256,AF_MP) = k^T zero-padded.  Writes dS (B,4,n,AF_MP) and dq (B,n,256).
+// One wave = 4 query rows x 4 heads, as in the forward.  P: the forward's (B,4,n,TA_MP) (zero on padded keys, so dS is too);
+// kt (B,256,TA_MP) = k^T zero-padded.  Writes dS (B,4,n,TA_MP) and dq (B,n,256).
 __global__ __launch_bounds__(256) void token_attn_f32_bwd_dq_kernel(const float *__restrict__ dout, const float *__restrict__ v, int ldv,
                                                                     const float *__restrict__ P, const float *__restrict__ kt, int n, int m,
                                                                     float scale, float *__restrict__ dS, float *__restrict__ dq) {
-  __shared__ __attribute__((aligned(16))) float Sl[4][16][AF_MP + 4];
+  __shared__ __attribute__((aligned(16))) float Sl[4][16][TA_MP + 4];
   const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n0 = (blockIdx.x * 4 + wave) * 4;
   if (n0 >= n) return;
@@ -204,89 +188,40 @@ __global__ __launch_bounds__(256) void token_attn_f32_bwd_dq_kernel(const float 
   const bool a_valid = n0 + a_nl < n, row_ok = n0 + kg < n;
   const float *G = dout + ((size_t)b * n + n0 + a_nl) * 256;
   const float *V = v + (size_t)b * m * ldv;
-  struct Raw {
-    float4 a, b;
-  };
-  auto ld8 = [](const float *p) { return Raw{*reinterpret_cast<const float4 *>(p), *reinterpret_cast<const float4 *>(p + 4)}; };
-  auto sp8 = [](const Raw &r) {
-    const float v[8] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w};
-    return split8_bf16(v);
-  };
-  constexpr int AF_PF = AF_PF_DEPTH, NPAIR = 8 * AF_NT;
   // dP: the forward's score loop with (dO, v) in place of (q, k)
-  f32x4 acc[AF_NT];
+  f32x4 acc[TA_NT];
 #pragma unroll
-  for (int t = 0; t < AF_NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nt_valid = (m + 15) >> 4;
-  {
-    auto addr = [&](int i) { return V + (size_t)min((i % AF_NT) * 16 + li, m - 1) * ldv + (i / AF_NT) * 32 + kg * 8; };
-    Raw ring[AF_PF];
-#pragma unroll
-    for (int i = 0; i < AF_PF; ++i) ring[i] = ld8(addr(i));
-    bf16x8_hl a = af_zero();
-#pragma unroll
-    for (int i = 0; i < NPAIR; ++i) {
-      const int ks = i / AF_NT, t = i % AF_NT;
-      if (t == 0) {
-        const int kk = ks * 32 + kg * 8;
-        a = af_zero();
-        if (a_valid && (kk >> 6) == a_h) a = af_load8(G + kk);
-      }
-      const Raw cur = ring[i % AF_PF];
-      if (i + AF_PF < NPAIR) ring[i % AF_PF] = ld8(addr(i + AF_PF));
-      if (t < nt_valid) acc[t] = mfma3_hh_hl_lh_16x16(a, sp8(cur), acc[t]);
-    }
-  }
+  for (int t = 0; t < TA_NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  af_scores([&](int ks) { return af_head_frag(G, a_valid, a_h, kg, ks); }, V, ldv, m, (m + 15) >> 4, li, kg, acc);
   // acc[t][h]: dP of query n0 + kg, head h, key t * 16 + li
-  const size_t hstride = (size_t)n * AF_MP;
-  const size_t prow = ((size_t)b * 4 * n + n0 + kg) * AF_MP + li;
-  float p[AF_NT][4], dl[4] = {0.f, 0.f, 0.f, 0.f};
+  const size_t hstride = (size_t)n * TA_MP;
+  const size_t prow = ((size_t)b * 4 * n + n0 + kg) * TA_MP + li;
+  float p[TA_NT][4], dl[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int t = 0; t < AF_NT; ++t)
+  for (int t = 0; t < TA_NT; ++t)
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
       p[t][h] = row_ok ? P[prow + h * hstride + t * 16] : 0.f;
       dl[h] = fmaf(p[t][h], acc[t][h], dl[h]);
     }
 #pragma unroll
-  for (int h = 0; h < 4; ++h) {
-    float v = dl[h];
-    v += af_swz<1>(v); v += af_swz<2>(v); v += af_swz<4>(v); v += af_swz<8>(v);
-    dl[h] = v;
-  }
+  for (int h = 0; h < 4; ++h) dl[h] = row16_sum(dl[h]);
 #pragma unroll
-  for (int t = 0; t < AF_NT; ++t)
+  for (int t = 0; t < TA_NT; ++t)
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
       const float ds = p[t][h] * (acc[t][h] - dl[h]);
       Sl[wave][kg * 4 + h][t * 16 + li] = ds;
       if (row_ok) dS[prow + h * hstride + t * 16] = ds;
     }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_handover();
   // dq: the forward's P v loop with (dS, k^T) in place of (P, v^T)
-  bf16x8_hl sa[AF_MP / 32];
+  bf16x8_hl sa[TA_MP / 32];
 #pragma unroll
-  for (int ks = 0; ks < AF_MP / 32; ++ks) sa[ks] = af_load8(&Sl[wave][li][ks * 32 + kg * 8]);
-  const float *KT = kt + (size_t)b * 256 * AF_MP;
-  {
-    constexpr int NKS = AF_MP / 32, NP2 = 16 * NKS;
-    auto addr = [&](int i) { return KT + (size_t)((i / NKS) * 16 + li) * AF_MP + kg * 8 + (i % NKS) * 32; };
-    Raw ring[AF_PF];
-#pragma unroll
-    for (int i = 0; i < AF_PF; ++i) ring[i] = ld8(addr(i));
-    f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < NP2; ++i) {
-      const int nt = i / NKS, ks = i % NKS;
-      if (ks == 0) o = f32x4{0.f, 0.f, 0.f, 0.f};
-      const Raw cur = ring[i % AF_PF];
-      if (i + AF_PF < NP2) ring[i % AF_PF] = ld8(addr(i + AF_PF));
-      o = mfma3_hh_hl_lh_16x16(sa[ks], sp8(cur), o);
-      if (ks == NKS - 1 && row_ok) dq[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = o[nt >> 2] * scale;
-    }
-  }
+  for (int ks = 0; ks < TA_MP / 32; ++ks) sa[ks] = af_load8(&Sl[wave][li][ks * 32 + kg * 8]);
+  af_apply(sa, kt + (size_t)b * 256 * TA_MP, li, kg, [&](int nt, float o) {
+    if (row_ok) dq[((size_t)b * n + n0 + kg) * 256 + nt * 16 + li] = o * scale;
+  });
 }
 
 // RPE terms: one wave per query row i; lane l owns channels 4 l .. 4 l + 3 of every key's E row (one coalesced 1 KiB row per key).
@@ -295,17 +230,15 @@ constexpr int AB_UNROLL = 8;  // E rows in flight per wave
 __global__ __launch_bounds__(256) void token_attn_f32_bwd_rpe_kernel(const float *__restrict__ dS, const float *__restrict__ qp, int ldqp,
                                                                      const float *__restrict__ E, int n, int m, float scale,
                                                                      float *__restrict__ dqp, float *__restrict__ dE) {
-  __shared__ __attribute__((aligned(16))) float4 Sl[4][AF_MP];  // [wave][key]: scale dS of the 4 heads
+  __shared__ __attribute__((aligned(16))) float4 Sl[4][TA_MP];  // [wave][key]: scale dS of the 4 heads
   const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * 4 + wave;
   if (i >= n) return;
-  const size_t row = (size_t)b * n + i, hstride = (size_t)n * AF_MP;
-  const float *S = dS + ((size_t)b * 4 * n + i) * AF_MP;
+  const size_t row = (size_t)b * n + i, hstride = (size_t)n * TA_MP;
+  const float *S = dS + ((size_t)b * 4 * n + i) * TA_MP;
   for (int j = lane; j < m; j += 64)
     Sl[wave][j] = make_float4(scale * S[j], scale * S[hstride + j], scale * S[2 * hstride + j], scale * S[3 * hstride + j]);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_handover();
   float4 qv[4], acc[4];
 #pragma unroll
   for (int h = 0; h < 4; ++h) {
@@ -366,14 +299,14 @@ __global__ __launch_bounds__(256) void token_attn_f32_bwd_dkv_kernel(const float
     a.z = fmaf(s, x.z, a.z);
     a.w = fmaf(s, x.w, a.w);
   };
-  const size_t pbase = ((size_t)b * 4 + h) * n * AF_MP + j0;
+  const size_t pbase = ((size_t)b * 4 + h) * n * TA_MP + j0;
   for (int i0 = 0; i0 < n; i0 += AB_IC) {
     __syncthreads();
     {
       const int r = tid >> 3, k4 = (tid & 7) * 4, c8 = (tid & 7) * 8;
       const bool ok = i0 + r < n;
       auto ld4 = [&](const float *p) { return ok ? *reinterpret_cast<const float4 *>(p) : make_float4(0.f, 0.f, 0.f, 0.f); };
-      const size_t pi = pbase + (size_t)(i0 + r) * AF_MP + k4;  // j0 + k4 + 3 < AF_MP: the padded width holds every tile
+      const size_t pi = pbase + (size_t)(i0 + r) * TA_MP + k4;  // j0 + k4 + 3 < TA_MP: the padded width holds every tile
       *reinterpret_cast<float4 *>(&sS[r][k4]) = ld4(dS + pi);
       *reinterpret_cast<float4 *>(&sP[r][k4]) = ld4(P + pi);
       const float *qr = q + ((size_t)b * n + i0 + r) * ldq + h * 64 + c8;
@@ -529,9 +462,7 @@ __global__ __launch_bounds__(256) void vit_attn_f32_kernel(const float *__restri
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) Ot[wave][col][t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb] = o[t][r] * inv;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_handover();
   // 32 rows x 256 B: 16 lanes per row, 16 B each
 #pragma unroll
   for (int it = 0; it < 8; ++it) {
@@ -561,45 +492,34 @@ using namespace unopose;
 
 extern "C" {
 
+// The eval (P null) and the training forward (P: the saved softmax) behind one launcher; `name`: the entry point, for the error texts
+static int launch_token_attn_f32(const char *name, const float *q, int ldq, const float *k, int ldk, const float *vt, const float *qp,
+                                 int ldqp, const float *E, int B, int n, int m, float scale, float *out, float *P,
+                                 unopose_stream_t stream) {
+  UNOPOSE_REQUIRE(q && k && vt && out, "%s: null pointer", name);
+  UNOPOSE_REQUIRE((qp == nullptr) == (E == nullptr), "%s: qp and E go together", name);
+  UNOPOSE_REQUIRE(B >= 0 && n >= 1 && m >= 1 && m <= TA_MP && B <= 65535, "%s: m=%d exceeds the %d-key tile", name, m, TA_MP);
+  UNOPOSE_REQUIRE(ldq >= 256 && ldk >= 256 && ldq % 8 == 0 && ldk % 8 == 0 && (!E || (ldqp >= 1024 && ldqp % 8 == 0)),
+                  "%s: row strides must be multiples of 8 elements", name);
+  if (B == 0) return UNOPOSE_OK;
+  auto *kernel = E ? (P ? token_attn_f32_kernel<true, true> : token_attn_f32_kernel<true, false>)
+                   : (P ? token_attn_f32_kernel<false, true> : token_attn_f32_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(cdiv(n, 16), B), dim3(256), 0, (hipStream_t)stream, q, ldq, k, ldk, vt, qp, ldqp, E, n, m, scale, out, P);
+  return check_launch(name);
+}
+
 int unopose_token_attention_f32(const float *q, int ldq, const float *k, int ldk, const float *vt, const float *qp,
                                 int ldqp, const float *E, int B, int n, int m, float scale, float *out,
                                 unopose_stream_t stream) {
-  UNOPOSE_REQUIRE(q && k && vt && out, "token_attention_f32: null pointer");
-  UNOPOSE_REQUIRE((qp == nullptr) == (E == nullptr), "token_attention_f32: qp and E go together");
-  UNOPOSE_REQUIRE(B >= 0 && n >= 1 && m >= 1 && m <= AF_MP && B <= 65535,
-                  "token_attention_f32: m=%d exceeds the %d-key tile", m, AF_MP);
-  UNOPOSE_REQUIRE(ldq >= 256 && ldk >= 256 && ldq % 8 == 0 && ldk % 8 == 0 && (!E || (ldqp >= 1024 && ldqp % 8 == 0)),
-                  "token_attention_f32: row strides must be multiples of 8 elements");
-  if (B == 0) return UNOPOSE_OK;
-  dim3 grid(cdiv(n, 16), B);
-  hipStream_t s = (hipStream_t)stream;
-  if (E)
-    hipLaunchKernelGGL(token_attn_f32_kernel<true>, grid, dim3(256), 0, s, q, ldq, k, ldk, vt, qp, ldqp, E, n, m, scale,
-                       out, (float *)nullptr);
-  else
-    hipLaunchKernelGGL(token_attn_f32_kernel<false>, grid, dim3(256), 0, s, q, ldq, k, ldk, vt, (const float *)nullptr,
-                       0, (const float *)nullptr, n, m, scale, out, (float *)nullptr);
-  return check_launch("token_attention_f32");
+  return launch_token_attn_f32("token_attention_f32", q, ldq, k, ldk, vt, qp, ldqp, E, B, n, m, scale, out, nullptr, stream);
 }
 
 int unopose_token_attention_f32_train(const float *q, int ldq, const float *k, int ldk, const float *vt, const float *qp, int ldqp,
                                       const float *E, int B, int n, int m, float scale, float *out, float *P, unopose_stream_t stream) {
-  UNOPOSE_REQUIRE(q && k && vt && out && P, "token_attention_f32_train: null pointer");
-  UNOPOSE_REQUIRE((qp == nullptr) == (E == nullptr), "token_attention_f32_train: qp and E go together");
-  UNOPOSE_REQUIRE(B >= 0 && n >= 1 && m >= 1 && m <= AF_MP && B <= 65535,
-                  "token_attention_f32_train: m=%d exceeds the %d-key tile", m, AF_MP);
-  UNOPOSE_REQUIRE(ldq >= 256 && ldk >= 256 && ldq % 8 == 0 && ldk % 8 == 0 && (!E || (ldqp >= 1024 && ldqp % 8 == 0)),
-                  "token_attention_f32_train: row strides must be multiples of 8 elements");
-  if (B == 0) return UNOPOSE_OK;
-  dim3 grid(cdiv(n, 16), B);
-  hipStream_t s = (hipStream_t)stream;
-  if (E)
-    hipLaunchKernelGGL((token_attn_f32_kernel<true, true>), grid, dim3(256), 0, s, q, ldq, k, ldk, vt, qp, ldqp, E, n, m, scale, out, P);
-  else
-    hipLaunchKernelGGL((token_attn_f32_kernel<false, true>), grid, dim3(256), 0, s, q, ldq, k, ldk, vt, (const float *)nullptr, 0,
-                       (const float *)nullptr, n, m, scale, out, P);
-  return check_launch("token_attention_f32_train");
+  UNOPOSE_REQUIRE(P, "token_attention_f32_train: null pointer");
+  return launch_token_attn_f32("token_attention_f32_train", q, ldq, k, ldk, vt, qp, ldqp, E, B, n, m, scale, out, P, stream);
 }
+
 
 int unopose_token_attention_f32_backward(const float *dout, const float *q, int ldq, const float *v, int ldv, const float *kt,
                                          const float *qp, int ldqp, const float *E, const float *P, int B, int n, int m, float scale,
@@ -607,8 +527,8 @@ int unopose_token_attention_f32_backward(const float *dout, const float *q, int 
   UNOPOSE_REQUIRE(dout && q && v && kt && P && dS && dq && dk && dv, "token_attention_f32_backward: null pointer");
   UNOPOSE_REQUIRE((qp == nullptr) == (E == nullptr) && (qp == nullptr) == (dqp == nullptr) && (dE == nullptr || E != nullptr),
                   "token_attention_f32_backward: qp, E and dqp go together (dE only with them)");
-  UNOPOSE_REQUIRE(B >= 0 && n >= 1 && m >= 1 && m <= AF_MP && B <= 65535,
-                  "token_attention_f32_backward: m=%d exceeds the %d-key tile", m, AF_MP);
+  UNOPOSE_REQUIRE(B >= 0 && n >= 1 && m >= 1 && m <= TA_MP && B <= 65535,
+                  "token_attention_f32_backward: m=%d exceeds the %d-key tile", m, TA_MP);
   UNOPOSE_REQUIRE(ldq >= 256 && ldv >= 256 && ldq % 8 == 0 && ldv % 8 == 0 && (!qp || (ldqp >= 1024 && ldqp % 8 == 0)),
                   "token_attention_f32_backward: row strides must be multiples of 8 elements");
   if (B == 0) return UNOPOSE_OK;

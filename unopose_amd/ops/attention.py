@@ -106,6 +106,7 @@ def _token_attention_hip_f32(x, mem, att, embed):
     fp32 with the RPE fold baked into the weights (exact algebra, fp32 rounding)."""
 
     B, n, C = x.shape
+    kp = _key_pad()
     m = mem.shape[1]
     rpe = embed is not None
     key = _params_key(att, rpe, "f32")
@@ -125,12 +126,12 @@ def _token_attention_hip_f32(x, mem, att, embed):
     _, w_q, b_q, w_kv, b_kv = cache
     yq = linear_f32_raw(x, w_q, b_q, att, "q")
     ykv = linear_f32_raw(mem, w_kv, b_kv, att, "kv")
-    if ykv.is_contiguous() and C % 32 == 0 and m <= _KEY_PAD:  # V^T, zero-padded to the kernel's key count: one launch (csrc/glue.hip)
-        vt = torch.empty(B, C, _KEY_PAD, dtype=torch.float32, device=x.device)
+    if ykv.is_contiguous() and C % 32 == 0 and m <= kp:  # V^T, zero-padded to the kernel's key count: one launch (csrc/glue.hip)
+        vt = torch.empty(B, C, kp, dtype=torch.float32, device=x.device)
         with on_device(x.device):
-            call("unopose_transpose_pad_f32", ctypes.c_void_p(ykv.data_ptr() + C * 4), ykv.stride(1), B, m, C, _KEY_PAD, ptr(vt), stream_ptr())
+            call("unopose_transpose_pad_f32", ctypes.c_void_p(ykv.data_ptr() + C * 4), ykv.stride(1), B, m, C, kp, ptr(vt), stream_ptr())
     else:
-        vt = torch.zeros(B, C, _KEY_PAD, dtype=torch.float32, device=x.device)
+        vt = torch.zeros(B, C, kp, dtype=torch.float32, device=x.device)
         vt[:, :, :m] = ykv[..., C:].transpose(1, 2)
     E = _c(embed.float()) if rpe else None
     out = torch.empty(B, n, C, dtype=torch.float32, device=x.device)
@@ -172,22 +173,23 @@ def _attn_weights(att, rpe):
 
 def _token_attention_hip(x, mem, att, embed):
     B, n, C = x.shape
+    kp = _key_pad()
     m = mem.shape[1]
     bf = torch.bfloat16
     rpe = embed is not None
     w_q, b_q, w_kv, b_kv, w_all, b_all, bq32, bkv32, ball32 = _attn_weights(att, rpe)
     nq = w_q.shape[0]
     xb = x.to(bf)
-    vt = torch.empty(B, C, _KEY_PAD, dtype=bf, device=x.device)
+    vt = torch.empty(B, C, kp, dtype=bf, device=x.device)
 
     def project_kv(a2, w, b32, rows):
         """a2 @ w^T + b with the V columns (the last 256) written straight into `vt` (csrc/gemm_small.hip EPI 4): no transpose launch"""
         y = torch.empty(rows, w.shape[0], dtype=bf, device=x.device)
         with on_device(x.device):
-            call("unopose_linear_bf16_kv_vt", ptr(a2), ptr(w), ptr(b32), ptr(y), ptr(vt), rows, w.shape[0], C, m, _KEY_PAD, stream_ptr())
+            call("unopose_linear_bf16_kv_vt", ptr(a2), ptr(w), ptr(b32), ptr(y), ptr(vt), rows, w.shape[0], C, m, kp, stream_ptr())
         return y
 
-    fused_vt = st.USE_KV_VT and C == 256 and _KEY_PAD - m <= 64 and st.USE_HIP_GEMM and st.HIP_GEMM_ALL
+    fused_vt = st.USE_KV_VT and C == 256 and kp - m <= 64 and st.USE_HIP_GEMM and st.HIP_GEMM_ALL
     with torch.autocast("cuda", enabled=False):
         if mem is x:  # self-attention: one GEMM for q | qp | k | v
             if fused_vt:
@@ -204,7 +206,7 @@ def _token_attention_hip(x, mem, att, embed):
     # q | qp and k | v are consumed in place from the projection outputs (row strides passed to the kernel)
     if not fused_vt:
         with on_device(x.device):
-            call("unopose_transpose_pad_bf16", ctypes.c_void_p(ykv.data_ptr() + C * 2), ykv.stride(1), B, m, C, _KEY_PAD, ptr(vt), stream_ptr())
+            call("unopose_transpose_pad_bf16", ctypes.c_void_p(ykv.data_ptr() + C * 2), ykv.stride(1), B, m, C, kp, ptr(vt), stream_ptr())
     E = _c(embed.to(bf)) if rpe else None
     out = torch.empty(B, n, C, dtype=bf, device=x.device)
     esz = 2
