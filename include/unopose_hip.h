@@ -235,6 +235,7 @@ int unopose_infonce_grad(const float *x, int B, int R, int C, const float *stats
  * statistics followed by ReLU), x / y / dy / dx (B, C, L) fp32 with L = N * S a multiple of 4.  forward: batch mean / rstd (biased
  * variance) into `mean`, `rstd`, running statistics updated as nn.BatchNorm2d does (unbiased variance; both NULL: not tracked),
  * y = relu(bn(x)).  backward: dgamma, dbeta, dx from x, dy and the forward's mean / rstd (the ReLU mask is recomputed).
+ * The statistics are the chunks' (mean, centred sum of squares) combined in double: sound however far a channel sits from zero.
  * workspace: 2 * B * C * ceil(L / unopose_bn_train_chunk()) floats. */
 int unopose_bn_train_chunk(void);
 int unopose_bn_relu_train_forward(const float *x, int B, int C, long L, const float *gamma, const float *beta, float eps, float momentum,

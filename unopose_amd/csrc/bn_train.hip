@@ -4,10 +4,11 @@
 // (MIOpenBatchNormFwdTrainSpatial / BwdSpatial: 73.6 ms of the 254 ms step at BASELINE configs[3], ~2 TB/s on tensors of up to
 // 4.3 GB) and the separate ReLU forward / threshold-backward passes.  The tensors are (B, C, N, S) fp32, channel-major slabs of
 // L = N * S contiguous values, so everything is streaming work:
-//   forward   stats pass (sum, sum of squares per (b, c) chunk -> fp32 partials, combined in double per channel, running statistics
-//             updated exactly as nn.BatchNorm2d does: biased variance for the normalisation, unbiased for running_var) + apply pass
-//             y = max(x a + b, 0),  a = gamma rstd,  b = beta - mean a;
-//   backward  reduction pass (sum dz, sum dz xhat with dz = dy [x a + b > 0], xhat = (x - mean) rstd: the ReLU mask is RECOMPUTED
+//   forward   stats pass (mean and centred sum of squares M2 of each (b, c) chunk, taken about the chunk's own values -> fp32 partials,
+//             combined in double per channel by Chan's parallel formula: never E[x^2] - E[x]^2, whose error grows with (mean / sigma)^2;
+//             running statistics updated exactly as nn.BatchNorm2d does: biased variance for the normalisation, unbiased for
+//             running_var) + apply pass y = max((x - mean) a + beta, 0),  a = gamma rstd;
+//   backward  reduction pass (sum dz, sum dz xhat with dz = dy [(x - mean) a + beta > 0], xhat = (x - mean) rstd: the ReLU mask is RECOMPUTED
 //             from x, nothing but x, mean, rstd is kept from the forward) + apply pass dx = a (dz - dbeta / M - xhat dgamma / M).
 // Every pass moves 16 bytes per lane per access; a workgroup owns one chunk of one (b, c) slab, so scale and shift are scalars.
 #include "common.h"
@@ -15,6 +16,11 @@
 namespace unopose {
 
 constexpr int BN_CHUNK = 16384;  // elements of a slab per workgroup (256 threads x 16 float4)
+
+// The pre-activation z = gamma xhat + beta.  Forward, both backward passes and the pool kernels evaluate it by THIS expression
+// (a = gamma rstd), so the ReLU mask the backward recomputes is the forward's bit for bit; x - mean is exact or nearly so where it
+// matters (Sterbenz), which a folded shift beta - mean a is not once |mean| >> sigma.
+__device__ __forceinline__ float bn_preact(float x, float mean, float a, float beta) { return fmaf(x - mean, a, beta); }
 
 __device__ __forceinline__ float2 block_sum2(float a, float b, float2 *red) {
   a = wave_sum_f32(a);
@@ -30,40 +36,68 @@ __device__ __forceinline__ float2 block_sum2(float a, float b, float2 *red) {
   return r;
 }
 
-// part[((c * B + b) * nchunk + chunk)] = (sum x, sum x^2) of that chunk
+// part[((c * B + b) * nchunk + chunk)] = (mean, M2 = sum (x - mean)^2) of that chunk, both ABOUT THE CHUNK'S OWN DATA: nothing here is a
+// difference of two sums that grow with the channel's offset.  The chunk's 64 values per lane stay in registers (x is read once):
+//   sweep 1  m0 = K + sum (x - K) / n with K the chunk's first element;
+//   sweep 2  s = sum (x - m0), q = sum (x - m0)^2  ->  mean = m0 + s / n,  M2 = q - s^2 / n   (s is rounding-sized: no cancellation).
+// A constant chunk gives (its value, 0) exactly.
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float *__restrict__ x, int C, long L, int nchunk, float2 *__restrict__ part) {
-  __shared__ float2 red[4];
+  __shared__ float2 red[2][4];
   const int chunk = blockIdx.x, c = blockIdx.y, b = blockIdx.z, B = gridDim.z;
   const float *p = x + ((size_t)b * C + c) * L;
   const long e0 = (long)chunk * BN_CHUNK, e1 = min(e0 + BN_CHUNK, L);
-  float s = 0.f, ss = 0.f;
-  for (long e = e0 + threadIdx.x * 4; e < e1; e += 256 * 4) {
-    const float4 v = *reinterpret_cast<const float4 *>(p + e);
-    s += (v.x + v.y) + (v.z + v.w);
-    ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+  const float K = p[e0], inv_n = 1.f / (float)(e1 - e0);
+  float4 v[BN_CHUNK / 1024];
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < BN_CHUNK / 1024; ++i) {
+    const long e = e0 + (i * 256 + threadIdx.x) * 4;
+    if (e < e1) {
+      v[i] = *reinterpret_cast<const float4 *>(p + e);
+      s += ((v[i].x - K) + (v[i].y - K)) + ((v[i].z - K) + (v[i].w - K));
+    }
   }
-  const float2 r = block_sum2(s, ss, red);
-  if (threadIdx.x == 0) part[((size_t)c * B + b) * nchunk + chunk] = r;
+  const float m0 = K + block_sum2(s, 0.f, red[0]).x * inv_n;
+  float q = 0.f;
+  s = 0.f;
+#pragma unroll
+  for (int i = 0; i < BN_CHUNK / 1024; ++i) {
+    if (e0 + (i * 256 + threadIdx.x) * 4 < e1) {
+      const float d0 = v[i].x - m0, d1 = v[i].y - m0, d2 = v[i].z - m0, d3 = v[i].w - m0;
+      s += (d0 + d1) + (d2 + d3);
+      q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+  }
+  const float2 r = block_sum2(s, q, red[1]);
+  if (threadIdx.x == 0) part[((size_t)c * B + b) * nchunk + chunk] = make_float2(m0 + r.x * inv_n, fmaxf(r.y - r.x * r.x * inv_n, 0.f));
 }
 
-// one workgroup per channel: mean / rstd of the batch, running statistics (momentum < 0: cumulative average with `count` batches seen)
-__global__ __launch_bounds__(64) void bn_finalize_kernel(const float2 *__restrict__ part, int per_channel, double count, float eps,
-                                                         float momentum, float *__restrict__ mean_out, float *__restrict__ rstd_out,
+// one workgroup per channel: mean / rstd of the batch, running statistics (momentum < 0: cumulative average with `count` batches seen).
+// The chunks' (mean, M2) are combined in double by Chan's formula, M2 = sum M2_i + sum n_i (mean_i - mean)^2, the channel mean itself
+// taken about the first chunk's; n_i follows from the chunk's index (per_channel = B * nchunk partials, the last of a slab ragged).
+__global__ __launch_bounds__(64) void bn_finalize_kernel(const float2 *__restrict__ part, int per_channel, int nchunk, long L, double count,
+                                                         float eps, float momentum, float *__restrict__ mean_out, float *__restrict__ rstd_out,
                                                          float *__restrict__ running_mean, float *__restrict__ running_var) {
   const int c = blockIdx.x;
-  double s = 0.0, ss = 0.0;
+  const float2 *pc = part + (size_t)c * per_channel;
+  const double ref = (double)pc[0].x;
+  double s = 0.0;
   for (int i = threadIdx.x; i < per_channel; i += 64) {
-    const float2 v = part[(size_t)c * per_channel + i];
-    s += (double)v.x;
-    ss += (double)v.y;
+    const double n = (double)min((long)BN_CHUNK, L - (long)(i % nchunk) * BN_CHUNK);
+    s += n * ((double)pc[i].x - ref);
   }
-  for (int d = 32; d >= 1; d >>= 1) {
-    s += __shfl_xor(s, d);
-    ss += __shfl_xor(ss, d);
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+  const double mean = ref + s / count;
+  double m2 = 0.0;
+  for (int i = threadIdx.x; i < per_channel; i += 64) {
+    const double n = (double)min((long)BN_CHUNK, L - (long)(i % nchunk) * BN_CHUNK);
+    const float2 v = pc[i];
+    const double d = (double)v.x - mean;
+    m2 += (double)v.y + n * d * d;
   }
+  for (int d = 32; d >= 1; d >>= 1) m2 += __shfl_xor(m2, d);
   if (threadIdx.x == 0) {
-    const double mean = s / count;
-    const double var = fmax(ss / count - mean * mean, 0.0);  // biased: what normalises the batch
+    const double var = m2 / count;  // biased: what normalises the batch
     mean_out[c] = (float)mean;
     rstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
     if (running_mean) {
@@ -79,15 +113,15 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const float *__restr
                                                             const float *__restrict__ beta, float *__restrict__ y) {
   const int chunk = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
   const size_t base = ((size_t)b * C + c) * L;
-  const float a = gamma[c] * rstd[c], sh = beta[c] - mean[c] * a;
+  const float m = mean[c], a = gamma[c] * rstd[c], bt = beta[c];
   const long e0 = (long)chunk * BN_CHUNK, e1 = min(e0 + BN_CHUNK, L);
   for (long e = e0 + threadIdx.x * 4; e < e1; e += 256 * 4) {
     const float4 v = *reinterpret_cast<const float4 *>(x + base + e);
     float4 o;
-    o.x = fmaxf(fmaf(v.x, a, sh), 0.f);
-    o.y = fmaxf(fmaf(v.y, a, sh), 0.f);
-    o.z = fmaxf(fmaf(v.z, a, sh), 0.f);
-    o.w = fmaxf(fmaf(v.w, a, sh), 0.f);
+    o.x = fmaxf(bn_preact(v.x, m, a, bt), 0.f);
+    o.y = fmaxf(bn_preact(v.y, m, a, bt), 0.f);
+    o.z = fmaxf(bn_preact(v.z, m, a, bt), 0.f);
+    o.w = fmaxf(bn_preact(v.w, m, a, bt), 0.f);
     *reinterpret_cast<float4 *>(y + base + e) = o;
   }
 }
@@ -100,7 +134,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_stats_kernel(const float *__r
   __shared__ float2 red[4];
   const int chunk = blockIdx.x, c = blockIdx.y, b = blockIdx.z, B = gridDim.z;
   const size_t base = ((size_t)b * C + c) * L;
-  const float m = mean[c], r = rstd[c], a = gamma[c] * r, sh = beta[c] - m * a;
+  const float m = mean[c], r = rstd[c], a = gamma[c] * r, bt = beta[c];
   const long e0 = (long)chunk * BN_CHUNK, e1 = min(e0 + BN_CHUNK, L);
   float s = 0.f, sx = 0.f;
   for (long e = e0 + threadIdx.x * 4; e < e1; e += 256 * 4) {
@@ -108,7 +142,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_stats_kernel(const float *__r
     const float xs[4] = {v.x, v.y, v.z, v.w}, gs[4] = {g.x, g.y, g.z, g.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float dz = fmaf(xs[i], a, sh) > 0.f ? gs[i] : 0.f;
+      const float dz = bn_preact(xs[i], m, a, bt) > 0.f ? gs[i] : 0.f;
       s += dz;
       sx += dz * ((xs[i] - m) * r);
     }
@@ -144,7 +178,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const float *__r
                                                                 float *__restrict__ dx) {
   const int chunk = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
   const size_t base = ((size_t)b * C + c) * L;
-  const float m = mean[c], r = rstd[c], a = gamma[c] * r, sh = beta[c] - m * a;
+  const float m = mean[c], r = rstd[c], a = gamma[c] * r, bt = beta[c];
   const float k0 = dbeta[c] * inv_count, k1 = dgamma[c] * inv_count;
   const long e0 = (long)chunk * BN_CHUNK, e1 = min(e0 + BN_CHUNK, L);
   for (long e = e0 + threadIdx.x * 4; e < e1; e += 256 * 4) {
@@ -153,7 +187,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const float *__r
     float o[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float dz = fmaf(xs[i], a, sh) > 0.f ? gs[i] : 0.f;
+      const float dz = bn_preact(xs[i], m, a, bt) > 0.f ? gs[i] : 0.f;
       o[i] = a * (dz - k0 - ((xs[i] - m) * r) * k1);
     }
     *reinterpret_cast<float4 *>(dx + base + e) = make_float4(o[0], o[1], o[2], o[3]);
@@ -179,12 +213,12 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const float *__res
     int bi = 0;
     if (row < rows) {
       const int c = (int)((row / N) % C);
-      const float a = gamma[c] * rstd[c], sh = beta[c] - mean[c] * a;
+      const float m = mean[c], a = gamma[c] * rstd[c], bt = beta[c];
       const float4 v = *reinterpret_cast<const float4 *>(x + row * S + 4 * li);
       const float xs[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float y = fmaxf(fmaf(xs[i], a, sh), 0.f);
+        const float y = fmaxf(bn_preact(xs[i], m, a, bt), 0.f);
         if (y > best) best = y, bi = 4 * li + i;
       }
     }
@@ -210,11 +244,11 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_stats_kernel(const fl
   __shared__ float2 red[4];
   const int c = blockIdx.x, b = blockIdx.y, B = gridDim.y;
   const size_t slab = (size_t)b * C + c;
-  const float m = mean[c], r = rstd[c], a = gamma[c] * r, sh = beta[c] - m * a;
+  const float m = mean[c], r = rstd[c], a = gamma[c] * r, bt = beta[c];
   float s = 0.f, sx = 0.f;
   for (int n = threadIdx.x; n < N; n += 256) {
     const float xv = x[(slab * N + n) * S + idx[slab * N + n]];
-    const float dz = fmaf(xv, a, sh) > 0.f ? g[slab * N + n] : 0.f;
+    const float dz = bn_preact(xv, m, a, bt) > 0.f ? g[slab * N + n] : 0.f;
     s += dz;
     sx += dz * ((xv - m) * r);
   }
@@ -236,7 +270,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_apply_kernel(const fl
     const long row = r0 + sub;
     if (row >= rows) continue;
     const int c = (int)((row / N) % C);
-    const float m = mean[c], r = rstd[c], a = gamma[c] * r, sh = beta[c] - m * a;
+    const float m = mean[c], r = rstd[c], a = gamma[c] * r, bt = beta[c];
     const float k0 = dbeta[c] * inv_count, k1 = dgamma[c] * inv_count;
     const int win = idx[row] - 4 * li;  // position of the winner inside this lane's four elements (or outside 0..3)
     const float gv = g[row];
@@ -245,7 +279,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_apply_kernel(const fl
     float o[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float dz = (i == win && fmaf(xs[i], a, sh) > 0.f) ? gv : 0.f;
+      const float dz = (i == win && bn_preact(xs[i], m, a, bt) > 0.f) ? gv : 0.f;
       o[i] = a * (dz - k0 - ((xs[i] - m) * r) * k1);
     }
     *reinterpret_cast<float4 *>(dx + row * S + 4 * li) = make_float4(o[0], o[1], o[2], o[3]);
@@ -270,8 +304,8 @@ int unopose_bn_relu_train_forward(const float *x, int B, int C, long L, const fl
   const int nchunk = cdiv(L, BN_CHUNK);
   dim3 grid(nchunk, C, B);
   hipLaunchKernelGGL(bn_stats_kernel, grid, dim3(256), 0, s, x, C, L, nchunk, (float2 *)workspace);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(64), 0, s, (const float2 *)workspace, B * nchunk, (double)B * (double)L, eps, momentum, mean,
-                     rstd, running_mean, running_var);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(64), 0, s, (const float2 *)workspace, B * nchunk, nchunk, L, (double)B * (double)L, eps, momentum,
+                     mean, rstd, running_mean, running_var);
   hipLaunchKernelGGL(bn_relu_apply_kernel, grid, dim3(256), 0, s, x, C, L, (const float *)mean, (const float *)rstd, gamma, beta, y);
   return check_launch("bn_relu_train_forward");
 }
@@ -307,8 +341,8 @@ int unopose_bn_relu_maxpool_train_forward(const float *x, int B, int C, int N, i
   const long L = (long)N * S, rows = (long)B * C * N;
   const int nchunk = cdiv(L, BN_CHUNK);
   hipLaunchKernelGGL(bn_stats_kernel, dim3(nchunk, C, B), dim3(256), 0, s, x, C, L, nchunk, (float2 *)workspace);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(64), 0, s, (const float2 *)workspace, B * nchunk, (double)B * (double)L, eps, momentum, mean,
-                     rstd, running_mean, running_var);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(64), 0, s, (const float2 *)workspace, B * nchunk, nchunk, L, (double)B * (double)L, eps, momentum,
+                     mean, rstd, running_mean, running_var);
 #define UNOPOSE_POOL_CASE(SS)                                                                                                                  \
   if (S == SS)                                                                                                                                 \
     hipLaunchKernelGGL(bn_relu_maxpool_kernel<SS>, dim3(pool_grid(rows, 256 / SS)), dim3(256), 0, s, x, C, rows, (const float *)mean,           \
