@@ -951,6 +951,30 @@ int unopose_match_train_backward(const void *xplanes, const void *yplanes, int B
                                  const float *Fc, const float *mc, const float *gc, const float *sc, const int *labc, const float *gL,
                                  float *dX, float *dsr, unopose_stream_t stream);
 
+/* Training items from rendered views (unopose_amd/provider_online.py: items_from_views_host is the specification; results equal it), for all
+ * views of a chunk of (query, reference) pairs.  Canvases: depth (., H, W) float32 in model units (0 = nothing), colour (., H, W, 3) uint8.
+ * unopose_items_ints(k): int32 per view-table row, per point descriptor, per crop descriptor, float64 per pair constant block, int32 per row
+ *     record, the minimum number of kept points; csrc/train_items.hip documents the layouts.  The caller has range-checked the descriptors.
+ * _views: V views; occ_slot[v] = the view's canvas in occ_depth / occ_rgb (-1: none; both may be null when no view has one), dilate[v] != 0:
+ *     the final mask is the visible mask grown by the L1 ball of radius 4 -> mask (V, H, W) bytes 0 / 1, scene_depth / scene_rgb (the nearer
+ *     surface, background 0), rows (V, H, 5) and table (V, 8): object / visible / final counts and the final mask's half-open extents.
+ * _points: D views (desc: source view, window, pair, valid), references (is_ref: draw among the set window pixels, spin, radius[pair] out) or
+ *     queries (centroid in the stated order, keep rule against radius[pair], draw among the kept, shift + noise) -> counts (D, 2) = set and
+ *     kept window pixels, pts (D, n_want, 3) float32, choose (D, n_want) int64.  keys: two uint64 per pair (reference draw, query draw);
+ *     pair_consts: spin (9) and shift (3) per pair; noise (pairs, n_want, 3) float64 (queries).  Scratch per view: win_rows and row_base max_side
+ *     int32 (win_rows = set pixels per window row, an output too), pix and kept max_side^2 int32, row_sums 3 max_side and drawn 3 n_want float64.
+ * _crops: D window crops (desc: source view, window, atlas row, mask offset) of scene_rgb and mask into atlas (., AW, 3) and the packed masks. */
+int unopose_items_ints(int what);
+int unopose_items_views(const float *obj_depth, const void *obj_rgb, const float *occ_depth, const void *occ_rgb, const int *occ_slot,
+                        const int *dilate, int V, int H, int W, void *mask, float *scene_depth, void *scene_rgb, int *rows, int *table,
+                        unopose_stream_t stream);
+int unopose_items_points(const void *mask, const float *scene_depth, int H, int W, const int *desc, const double *pair_consts, const void *keys,
+                         const double *noise, double fx, double fy, double cx, double cy, int D, int is_ref, int n_want, int S, int max_side,
+                         int *win_rows, int *row_base, int *pix, int *kept, double *row_sums, double *drawn, double *radius, int *counts,
+                         float *pts, void *choose, unopose_stream_t stream);
+int unopose_items_crops(const void *mask, const void *scene_rgb, int H, int W, const int *desc, int D, int max_h, int AW, void *atlas, void *packed,
+                        unopose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

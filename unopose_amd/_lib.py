@@ -181,6 +181,10 @@ SIGNATURES = {
     "unopose_coloraug_luma_sum": [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P],
     "unopose_coloraug_step": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "unopose_coloraug_blur_lines": [_P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P],
+    "unopose_items_ints": [_I],
+    "unopose_items_views": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "unopose_items_points": [_P, _P, _I, _I, _P, _P, _P, _P, _D, _D, _D, _D, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "unopose_items_crops": [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P],
 }
 
 

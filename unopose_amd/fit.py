@@ -19,6 +19,11 @@
   parameters only (``ColorAugmentor.plan``); ``collate_pairs_device`` ships the crops as one uint8 atlas and ``ops.finish_crops`` runs the
   augmentation, the mask, the resize and the normalisation on the rank's GPU when the batch is taken.  Same samples as the host route but for
   the grayscale operator's last bit (``ColorAugmentor``).  Off by default.
+* ``--online-models DIR`` (or ``dataloader.train.online.models=DIR``; ``--online-obj-ids`` / ``.obj_ids``): no dataset at all.  ``provider_online.OnlinePairs``
+  renders (query, reference) pairs of the folder's ``obj_XXXXXX.ply`` models on the rank's GPU and builds the items there (``dataloader.train.online.*``:
+  canvas, focal, fill, offset, occluder_prob, ssaa, shading, ambient, max_chunks; the provider's fields still come from ``dataloader.train.dataset.cfg``).
+  Batch i is a function of (seed, rank, i): ``--workers`` is ignored, ``--resume`` needs the iteration only.  ``--host`` builds the items with the numpy
+  rule from the renders read back (the same batches).  Off by default.
 * ranks: ``--gpus N`` starts N fresh processes before this one touches a GPU (RCCL through ``nccl``; ``gloo`` without GPUs); each runs
   ``freeze_backbone`` + ``wrap_ddp``.
 * rank 0 writes, into the output directory, ``model_{iteration:07d}.pth`` every ``period`` iterations (the newest ``max_to_keep`` are kept),
@@ -280,7 +285,9 @@ def run_settings(cfg, args, world=1):
                 amp=amp, seed=int(args.seed if args.seed is not None else tr.get("seed", 1)), log_period=int(tr.get("log_period", 50)),
                 batch_size=int(batch), workers=int(workers), output_dir=args.output_dir or cfg.get("misc", {}).get("output_dir"),
                 load_from=args.load_from or cfg.get("misc", {}).get("load_from") or None,
-                device_crops=bool(args.device_crops or dl.get("device_crops", False)))
+                device_crops=bool(args.device_crops or dl.get("device_crops", False)),
+                online_models=args.online_models or dl.get("online", {}).get("models") or None,
+                online_obj_ids=args.online_obj_ids or dl.get("online", {}).get("obj_ids") or None, online_host=bool(args.host))
 
 
 def _parser():
@@ -297,6 +304,10 @@ def _parser():
     ap.add_argument("--seed", type=int)
     ap.add_argument("--device-crops", action="store_true",
                     help="finish the crops of a batch on the GPU (colour augmentation, mask, resize, normalise); also dataloader.train.device_crops=true")
+    ap.add_argument("--online-models", help="train on pairs rendered on the GPU from this folder of obj_XXXXXX.ply models (provider_online.OnlinePairs) "
+                    "in place of the MegaPose files; also dataloader.train.online.models=DIR.  --workers is ignored")
+    ap.add_argument("--online-obj-ids", type=int, nargs="*", help="with --online-models: these objects only (default: every model of the folder)")
+    ap.add_argument("--host", action="store_true", help="with --online-models: build the items with the numpy rule from the renders read back")
     ap.add_argument("--print-plan", action="store_true", help="resolve the settings, print them as JSON and stop (touches no GPU)")
     ap.add_argument("opts", nargs="*", help="key=value overrides")
     return ap
@@ -345,11 +356,21 @@ def main(argv=None):
     dc = cfg["dataloader"]["train"]["dataset"]
     if s["device_crops"] and not on_gpu:
         raise SystemExit("--device-crops needs a GPU rank (--gpus >= 1)")
-    dataset = MegaPoseOneRefTrainSet(dc.get("cfg", dc), num_img_per_epoch=int(dc.get("num_img_per_epoch", -1)), seed=s["seed"] + rank,
-                                     device_crops=s["device_crops"])
+    if s["online_models"]:  # rendered pairs: no dataset state, no workers; batch i is a function of (seed, rank, i), so a resume needs the iteration only
+        if not on_gpu:
+            raise SystemExit("--online-models needs a GPU rank (--gpus >= 1)")
+        from .provider_online import OnlinePairs
 
-    def loader(iteration):
-        return build_loader(dataset, s["batch_size"], s["workers"], s["seed"], rank, world, start_iteration=iteration, pin_memory=on_gpu)
+        online = dict(cfg["dataloader"]["train"].get("online", {}))
+        dataset = None
+        loader = OnlinePairs(s["online_models"], dict(dc.get("cfg", dc), online=online), dev, s["seed"], rank=rank, world=world, host=s["online_host"],
+                             batch_size=s["batch_size"], obj_ids=s["online_obj_ids"])
+    else:
+        dataset = MegaPoseOneRefTrainSet(dc.get("cfg", dc), num_img_per_epoch=int(dc.get("num_img_per_epoch", -1)), seed=s["seed"] + rank,
+                                         device_crops=s["device_crops"])
+
+        def loader(iteration):
+            return build_loader(dataset, s["batch_size"], s["workers"], s["seed"], rank, world, start_iteration=iteration, pin_memory=on_gpu)
 
     try:
         fit(model, dataset, loader, optimizer, scheduler, s["output_dir"], s["max_iter"], period=s["period"], max_to_keep=s["max_to_keep"],
