@@ -86,7 +86,7 @@ __global__ __launch_bounds__(64) void bn_finalize_kernel(const float2 *__restric
     const double n = (double)min((long)BN_CHUNK, L - (long)(i % nchunk) * BN_CHUNK);
     s += n * ((double)pc[i].x - ref);
   }
-  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+  s = wave_all_sum(s);
   const double mean = ref + s / count;
   double m2 = 0.0;
   for (int i = threadIdx.x; i < per_channel; i += 64) {
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(64) void bn_finalize_kernel(const float2 *__restric
     const double d = (double)v.x - mean;
     m2 += (double)v.y + n * d * d;
   }
-  for (int d = 32; d >= 1; d >>= 1) m2 += __shfl_xor(m2, d);
+  m2 = wave_all_sum(m2);
   if (threadIdx.x == 0) {
     const double var = m2 / count;  // biased: what normalises the batch
     mean_out[c] = (float)mean;
@@ -161,10 +161,7 @@ __global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(const float2 *__res
     s += (double)v.x;
     sx += (double)v.y;
   }
-  for (int d = 32; d >= 1; d >>= 1) {
-    s += __shfl_xor(s, d);
-    sx += __shfl_xor(sx, d);
-  }
+  s = wave_all_sum(s), sx = wave_all_sum(sx);
   if (threadIdx.x == 0) {
     dbeta[c] = (float)s;
     dgamma[c] = (float)sx;

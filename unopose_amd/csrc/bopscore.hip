@@ -79,10 +79,7 @@ __global__ __launch_bounds__(256) void vsd_counts_kernel(const float *__restrict
       vsd_pixel(i, W, mt[i], mg[i], me[i], fx, fy, cx, cy, delta, diameter, taus, cnt);
   }
 #pragma unroll
-  for (int k = 0; k < VSD_COUNTS; ++k) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) cnt[k] += __shfl_xor(cnt[k], o, 64);
-  }
+  for (int k = 0; k < VSD_COUNTS; ++k) cnt[k] = wave_all_sum(cnt[k]);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) {
 #pragma unroll
@@ -98,11 +95,6 @@ __global__ __launch_bounds__(256) void vsd_counts_kernel(const float *__restrict
 // numpy's max / min: a NaN wins
 __device__ __forceinline__ double nan_max(double m, double v) { return (v > m || v != v) ? v : m; }
 __device__ __forceinline__ double nan_min(double m, double v) { return (v < m || v != v) ? v : m; }
-__device__ __forceinline__ double wave_nan_max(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = nan_max(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 __global__ __launch_bounds__(256) void pose_errors_kernel(const double *__restrict__ pts, int n, const double *__restrict__ syms, int S,
                                                          const double *__restrict__ est, const double *__restrict__ gt,
@@ -117,6 +109,7 @@ __global__ __launch_bounds__(256) void pose_errors_kernel(const double *__restri
 #pragma unroll
   for (int k = 0; k < 9; ++k) Kp[k] = K[k];
   const double inf = __builtin_inf();
+  const auto nmax = [](double m, double v) { return nan_max(m, v); };  // not symmetric: the wave's own value is the first operand
   double min_s = inf, min_p = inf;
   for (int s0 = 0; s0 < S; s0 += POSE_SYM_TILE) {
     const int tile = min(POSE_SYM_TILE, S - s0);
@@ -155,8 +148,8 @@ __global__ __launch_bounds__(256) void pose_errors_kernel(const double *__restri
       }
 #pragma unroll
       for (int j = 0; j < POSE_SYM_BLOCK; ++j) {
-        min_s = nan_min(min_s, wave_nan_max(ms[j]));
-        min_p = nan_min(min_p, wave_nan_max(mp[j]));
+        min_s = nan_min(min_s, wave_all(ms[j], nmax));
+        min_p = nan_min(min_p, wave_all(mp[j], nmax));
       }
     }
   }

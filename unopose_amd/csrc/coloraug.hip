@@ -74,8 +74,7 @@ __global__ __launch_bounds__(256) void coloraug_luma_sum_kernel(const uint8_t *_
     const uint8_t *p = src + ((size_t)(q[0] + y) * W + x) * 3;
     v = (unsigned)caug_luma(p[0], p[1], p[2]);
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = wave_all_sum(v);
   if ((threadIdx.x & 63) == 0) atomicAdd(sums + e[2], (unsigned long long)v);
 }
 

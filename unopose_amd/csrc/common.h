@@ -134,7 +134,22 @@ __device__ __forceinline__ BilinearTap bilinear_tap(long long pix, int H, int W,
   return t;
 }
 
-// ---- wave64 DPP reductions (gfx9 row_shr within the 16-lane rows; the four row results combined through v_readlane) --------
+// ---- wave64 reductions: TWO families, and a kernel keeps the one it was validated with --------------------------------------
+//  * DPP row_shr (wave_sum_f32, wave_max_f32, wave_max_u64 below): lane l of a 16-lane row accumulates lanes l-1, l-2, l-4, l-8 in
+//    turn, so lane 15 holds the row's result, and the four row results are combined as (r3 + r2) + (r1 + r0) (max: any order).  The
+//    result is wave-uniform (scalar registers).  The fp32 forward path uses it; block_sum_256 / block_max_256 extend it to 256 threads
+//    as (w0 + w1) + (w2 + w3).
+//  * xor butterfly (wave_all and its named forms below): v = op(v, v of lane ^ o) for o = 32, 16, ..., 1.  Both partners of a step
+//    compute the same two-operand result, so EVERY lane ends with the same bits: the data-side kernels (scoring, ground truth, dataset
+//    preparation, training items, mostly double and int) rely on that to match their host references.
+//  For integers, min and max the two agree.  For floating-point sums they add in different orders and differ in the last bits, so
+//  moving an existing kernel from one family to the other changes its results; new code picks the butterfly where every lane needs
+//  the value or the type is not fp32, the DPP form for an fp32 value wanted once per wave.
+//  Neither family, each with an order or a width of its own: row16_max / row16_sum (attn_common.h, 16-lane rows); optim.hip's
+//  block_sum_256 (LDS tree over 256 doubles); bn_train.hip's block_sum2 (wave partials added one after the other); the half-wave and
+//  sub-wave exchanges (__shfl_xor(., 32) in linattn.hip, attn_f32.hip, gemm_small.hip, fineassign.hip, linear_small_train.hip;
+//  la_head_sum; mt_sum4, mt_xor16, mt_xor32; the upward partial butterfly of gemm_kernel.h's LayerNorm epilogue); and the (value, index)
+//  arg-reductions of bn_train.hip, match_train.hip, posehead.hip, reftargets.hip and modelinfo.hip's cross-wave tie-break.
 // dpp_ctrl: row_shr:n = 0x110+n, row_bcast:15 = 0x142, row_bcast:31 = 0x143.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ uint32_t dpp_u32(uint32_t v, uint32_t identity) {
@@ -195,6 +210,59 @@ __device__ __forceinline__ float wave_max_f32(float v) {
 
 __device__ __forceinline__ int lane_id() {
   return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+}
+
+// sum / max over the 256 threads of a workgroup on the DPP family, `red`: 4 floats of LDS.  The barrier BEFORE the write lets calls
+// follow each other on the same `red`; there is none after the read.
+__device__ __forceinline__ float block_sum_256(float v, float *red /*[4]*/) {
+  v = wave_sum_f32(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ float block_max_256(float v, float *red) {
+  v = wave_max_f32(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// ---- xor butterfly over the 64 lanes: v = op(v, partner's v), partner = lane ^ 32, 16, ..., 1; the result is in every lane, with
+// the same bits.  The operand order is part of the contract (an op need not be symmetric).
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_all(T v, Op op) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
+  return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_all_sum(T v) {
+  return wave_all(v, [](T a, T b) { return a + b; });
+}
+__device__ __forceinline__ int wave_all_min(int v) {
+  return wave_all(v, [](int a, int b) { return min(a, b); });
+}
+__device__ __forceinline__ int wave_all_max(int v) {
+  return wave_all(v, [](int a, int b) { return max(a, b); });
+}
+__device__ __forceinline__ double wave_all_fmin(double v) {
+  return wave_all(v, [](double a, double b) { return fmin(a, b); });
+}
+__device__ __forceinline__ double wave_all_fmax(double v) {
+  return wave_all(v, [](double a, double b) { return fmax(a, b); });
+}
+
+// inclusive prefix sum over the 64 lanes (Hillis-Steele, __shfl_up by 1, 2, ..., 32); lane 63 holds the wave's total.
+template <typename T>
+__device__ __forceinline__ T wave_inclusive_sum(T v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
 }
 
 }  // namespace unopose

@@ -16,21 +16,6 @@
 
 namespace unopose {
 
-__device__ __forceinline__ float block_sum_256(float v, float *red /*[4]*/) {
-  v = wave_sum_f32(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ float block_max_256(float v, float *red) {
-  v = wave_max_f32(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 // Frame construction shared by the global and the per-point LRF, given
 //   z  : sign-resolved normal,  acc : sum_i alpha_i beta_i v_i  (model_utils.py:804-812)
 // x = acc / (|acc| + 1e-10) by MULTIPLICATION with the reciprocal here, by division in pe.hip's pe_frame_axes: the two forms differ in

@@ -289,23 +289,6 @@ namespace unopose {
 // `add`, `sigmoid`: the seven at::native kernels with packed fp32 instructions of tests/test_torch_glue_isa_gpu.py's reviewed list) --
 // tiny tensors, one launch each, deterministic reductions (fixed order, no atomics).
 
-__device__ __forceinline__ float block256_sum(float v, float *sh) {   // deterministic: wave sums, then the four partials in order
-  v = wave_sum_f32(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ float block256_max(float v, float *sh) {
-  v = wave_max_f32(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float r = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-  __syncthreads();
-  return r;
-}
-
 // radius[b] = max_i | p_i - mean(p) |  (oneref_grf_predator_pose_estimation_model.py: `torch.norm(pts - pts.mean(1), dim=2).max(1)[0]`)
 __global__ __launch_bounds__(256) void cloud_radius_kernel(const float *__restrict__ pts, int N, float *__restrict__ radius) {
   __shared__ float sh[4];
@@ -319,12 +302,7 @@ __global__ __launch_bounds__(256) void cloud_radius_kernel(const float *__restri
     sy += (double)P[3 * i + 1];
     sz += (double)P[3 * i + 2];
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    sx += __shfl_xor(sx, o);
-    sy += __shfl_xor(sy, o);
-    sz += __shfl_xor(sz, o);
-  }
+  sx = wave_all_sum(sx), sy = wave_all_sum(sy), sz = wave_all_sum(sz);
   if ((threadIdx.x & 63) == 0) shd[0][threadIdx.x >> 6] = sx, shd[1][threadIdx.x >> 6] = sy, shd[2][threadIdx.x >> 6] = sz;
   __syncthreads();
   const float mx = (float)(((shd[0][0] + shd[0][1]) + (shd[0][2] + shd[0][3])) / (double)N), my = (float)(((shd[1][0] + shd[1][1]) + (shd[1][2] + shd[1][3])) / (double)N),
@@ -334,7 +312,7 @@ __global__ __launch_bounds__(256) void cloud_radius_kernel(const float *__restri
     const float dx = P[3 * i] - mx, dy = P[3 * i + 1] - my, dz = P[3 * i + 2] - mz;
     r = fmaxf(r, sqrtf((dx * dx + dy * dy) + dz * dz));
   }
-  r = block256_max(r, sh);
+  r = block_max_256(r, sh);
   if (threadIdx.x == 0) radius[blockIdx.x] = r;
 }
 
@@ -426,8 +404,8 @@ __global__ __launch_bounds__(256) void pose_score_kernel(const float *__restrict
     s1 += D[i] < thr ? wi : 0.f;
     s2 += wi;
   }
-  s1 = block256_sum(s1, sh);
-  s2 = block256_sum(s2, sh);
+  s1 = block_sum_256(s1, sh);
+  s2 = block_sum_256(s2, sh);  // (its leading barrier follows every thread's read of s1's partials)
   if (threadIdx.x == 0) out[blockIdx.x] = s1 / (s2 + 1e-8f) * (s2 / (float)N);
 }
 

@@ -141,10 +141,7 @@ __global__ __launch_bounds__(256) void gt_visibility_kernel(const float *__restr
   gt_stream(canvas + (size_t)ix[0] * 9 * HW, g, wide, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256, mask ? mask + (size_t)p * HW : nullptr,
             mask ? mask_visib + (size_t)p * HW : nullptr, acc);
 #pragma unroll
-  for (int k = 0; k < GT_INTS; ++k) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) acc.v[k] = gt_combine(k, acc.v[k], __shfl_xor(acc.v[k], o, 64));
-  }
+  for (int k = 0; k < GT_INTS; ++k) acc.v[k] = wave_all(acc.v[k], [k](int a, int b) { return gt_combine(k, a, b); });
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) {
 #pragma unroll

@@ -85,12 +85,7 @@ __device__ __forceinline__ int lrf_ball_query(const float *sx, const float *sy, 
       const int w = w0 + lane;
       uint32_t bits = w < W ? g.bits[w] : 0u;
       const int pc = __builtin_popcount(bits);
-      int incl = pc;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-      }
+      const int incl = wave_inclusive_sum(pc, lane);
       int pos = cnt + incl - pc;
       while (bits) {
         const int bpos = __builtin_ctz(bits);

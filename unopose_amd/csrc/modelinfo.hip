@@ -39,22 +39,6 @@ __device__ __forceinline__ double dist2(double ax, double ay, double az, double 
   return (dx * dx + dy * dy) + dz * dz;
 }
 
-__device__ __forceinline__ double wave_fmax(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_fmin(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_add(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);  // every lane ends with the same bits
-  return v;
-}
-
 // The object's points of the launch: [lo, lo + cnt) of the packed array, or nothing if the table does not fit n_total.
 __device__ __forceinline__ bool object_range(const long long *__restrict__ offs, const long long *__restrict__ counts, int k, long long n_total,
                                              long long &lo, int &cnt) {
@@ -74,10 +58,8 @@ __device__ double farthest_from(const double *__restrict__ p, int n, double qx, 
     const double d = dist2(p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2], qx, qy, qz);
     if (d > best) best = d, at = i;  // increasing i: the first of a thread's ties stays
   }
-  const double wmax = wave_fmax(best);
-  int cand = best == wmax ? at : 0x7fffffff;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+  const double wmax = wave_all_fmax(best);
+  const int cand = wave_all_min(best == wmax ? at : 0x7fffffff);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) red[slot][wave] = wmax, red_i[slot][wave] = cand;
   __syncthreads();
@@ -120,7 +102,7 @@ __global__ __launch_bounds__(EXT_SCAN_THREADS) void pts_scan_kernel(const double
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    mn[c] = wave_fmin(mn[c]), mx[c] = wave_fmax(mx[c]);
+    mn[c] = wave_all_fmin(mn[c]), mx[c] = wave_all_fmax(mx[c]);
     if (lane == 0) red[c][wave] = mn[c], red[3 + c][wave] = mx[c];
   }
   __syncthreads();
@@ -137,7 +119,7 @@ __global__ __launch_bounds__(EXT_SCAN_THREADS) void pts_scan_kernel(const double
   double c3[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    sum[c] = wave_add(sum[c]);
+    sum[c] = wave_all_sum(sum[c]);
     if (lane == 0) red[c][wave] = sum[c];
   }
   __syncthreads();
@@ -220,7 +202,7 @@ __global__ __launch_bounds__(EXT_THREADS) void pts_pair_kernel(const double *__r
 #pragma unroll
     for (int j = 0; j < EXT_OWN; ++j) m = fmax(m, best[j]);
   }
-  m = wave_fmax(m);
+  m = wave_all_fmax(m);
   if (lane == 0) red[wave] = m;
   __syncthreads();
   if (threadIdx.x == 0) {

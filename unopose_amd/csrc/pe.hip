@@ -313,12 +313,7 @@ __global__ __launch_bounds__(PE_GW * 64) void pe_geometry_kernel(
     {  // exclusive scan of the PE_GCELLS counters: one cell per thread (of the first PE_GCELLS), wave scan, wave totals through LDS
       static_assert(PE_GW * 64 >= PE_GCELLS && PE_GCELLS % 64 == 0, "one cell per thread");
       const uint32_t c = tid < PE_GCELLS ? cnt32[tid] : 0u;
-      uint32_t incl = c;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-      }
+      const uint32_t incl = wave_inclusive_sum(c, lane);
       if (lane == 63) wtot[wave] = incl;
       __syncthreads();
       if (tid < PE_GCELLS) {

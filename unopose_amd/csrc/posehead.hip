@@ -463,7 +463,7 @@ __global__ __launch_bounds__(256) void topk_smallest_kernel(const float *__restr
 constexpr int TS_KMAX = 2048;
 __device__ __forceinline__ int ts_block_excl_scan(int v, int *wtot, int tid) {  // exclusive prefix sum over the 256 threads; wtot: 4 ints of LDS
   const int lane = tid & 63, wave = tid >> 6;
-  int incl = v;
+  int incl = v;  // common.h's wave_inclusive_sum, spelled out: through the call topk_select_kernel is scheduled in another order
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
     const int t = __shfl_up(incl, d);

@@ -34,17 +34,6 @@ constexpr int ADI_QUERIES = 2;
 constexpr int ADI_SLAB = ADI_THREADS * ADI_QUERIES;
 constexpr int ADI_TILE = 1024;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);  // every lane ends with the same bits
-  return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // degrees between two rotations as bop_eval.re forms them: the diagonal of R_e R^T (dot3_blas), added in order, clamped, acos.
 // Near 0 degrees one ulp of the cosine is 1e-6 degrees, so the trace has to carry the host's bits.
 __device__ __forceinline__ double rotation_error_deg(const double *Re, const double *R) {
@@ -94,7 +83,7 @@ __global__ __launch_bounds__(METRIC_THREADS) void pose_metrics_kernel(const doub
     const double dv = (Kp[3] * gx + Kp[4] * gy + Kp[5] * gz) / gw - (Kp[3] * ex + Kp[4] * ey + Kp[5] * ez) / ew;
     s_proj += sqrt(du * du + dv * dv);
   }
-  s_add = wave_sum(s_add), s_proj = wave_sum(s_proj);
+  s_add = wave_all_sum(s_add), s_proj = wave_all_sum(s_proj);
 
   double min_p = inf, min_r = inf, min_t = inf;
   for (int s0 = 0; s0 < S; s0 += METRIC_SYM_TILE) {
@@ -137,10 +126,10 @@ __global__ __launch_bounds__(METRIC_THREADS) void pose_metrics_kernel(const doub
         }
       }
 #pragma unroll
-      for (int j = 0; j < METRIC_SYM_BLOCK; ++j) min_p = fmin(min_p, wave_sum(sp[j]));
+      for (int j = 0; j < METRIC_SYM_BLOCK; ++j) min_p = fmin(min_p, wave_all_sum(sp[j]));
     }
   }
-  min_r = wave_min(min_r), min_t = wave_min(min_t);
+  min_r = wave_all_fmin(min_r), min_t = wave_all_fmin(min_t);
   // a wave without a symmetry block of its own still holds +inf in min_p
   if (lane == 0) red[wave][0] = s_add, red[wave][1] = s_proj, red[wave][2] = min_r, red[wave][3] = min_t, red[wave][4] = min_p;
   __syncthreads();
@@ -205,7 +194,7 @@ __global__ __launch_bounds__(ADI_THREADS) void adi_partial_kernel(const double *
 #pragma unroll
   for (int j = 0; j < ADI_QUERIES; ++j)
     if (slab * ADI_SLAB + j * ADI_THREADS + (int)threadIdx.x < n) s += sqrt(best[j]);
-  s = wave_sum(s);
+  s = wave_all_sum(s);
   if (lane == 0) red[wave] = s;
   __syncthreads();
   if (threadIdx.x == 0) {

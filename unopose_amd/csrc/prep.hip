@@ -25,13 +25,6 @@ namespace unopose {
 constexpr int PREP_DESC = 12;
 constexpr int PREP_DIST_PER_BLOCK = 2048;
 
-// sum over the 64 lanes in a fixed butterfly order: every lane ends with the same bits, whatever the launch
-__device__ __forceinline__ double prep_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void prep_crop_resize_kernel(const uint8_t *__restrict__ img, int W, int C, const int *__restrict__ desc,
                                                                const int *__restrict__ taps, const uint8_t *__restrict__ masks,
                                                                const float *__restrict__ lut, int S, int bgr, int use_mask,
@@ -105,7 +98,7 @@ __global__ __launch_bounds__(256) void prep_compact_lift_kernel(const double *__
     }
     base += __popcll(ballot);
   }
-  sx = prep_wave_sum(sx), sy = prep_wave_sum(sy), sz = prep_wave_sum(sz);
+  sx = wave_all_sum(sx), sy = wave_all_sum(sy), sz = wave_all_sum(sz);
   if (lane == 0) {
     double *o = row_sums + (size_t)(row_off + r) * 3;
     o[0] = sx, o[1] = sy, o[2] = sz;
@@ -126,7 +119,7 @@ __global__ __launch_bounds__(256) void prep_distances_kernel(const int *__restri
       const double *o = row_sums + (size_t)(row_off + r) * 3;
       sx += o[0], sy += o[1], sz += o[2];
     }
-    sx = prep_wave_sum(sx), sy = prep_wave_sum(sy), sz = prep_wave_sum(sz);
+    sx = wave_all_sum(sx), sy = wave_all_sum(sy), sz = wave_all_sum(sz);
     if (threadIdx.x == 0) centre[0] = sx / (double)n, centre[1] = sy / (double)n, centre[2] = sz / (double)n;
   }
   __syncthreads();

@@ -145,10 +145,10 @@ __global__ __launch_bounds__(64) void ref_finish_kernel(const long long *__restr
     const double t = __shfl_xor(near_t, o, 64);
     const int ti = __shfl_xor(near_i, o, 64), pi = __shfl_xor(pick, o, 64);
     const unsigned long long p = (unsigned long long)__shfl_xor((long long)prio, o, 64);
-    count += __shfl_xor(count, o, 64);
     if (nearer(t, ti, near_t, near_i)) near_t = t, near_i = ti;
     if (preferred(p, pi, prio, pick)) prio = p, pick = pi;
   }
+  count = wave_all_sum(count);
   if (lane == 0) {
     out[q] = pick;
     out[(size_t)Q + q] = count;

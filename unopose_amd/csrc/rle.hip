@@ -37,20 +37,11 @@ constexpr int RLE_FLAG_NEGATIVE = 1, RLE_FLAG_OVERLONG = 2, RLE_FLAG_MALFORMED =
 constexpr int RLE_FILL_PIXELS = 4096;  // output pixels per workgroup of rle_fill = run starts it can stage in LDS
 constexpr int RLE_MAX_BYTES = 12;      // bytes of one number: 60 data bits
 
-__device__ __forceinline__ long long rle_wave_scan(long long v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
 // inclusive prefix sum over the 256 threads of the workgroup, continued from `carry` (the same in every thread, advanced by the
 // workgroup's total).  Every thread of the workgroup calls it.
 __device__ __forceinline__ long long rle_block_scan(long long v, long long *wave_total, long long &carry) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = rle_wave_scan(v, lane);
+  v = wave_inclusive_sum(v, lane);
   __syncthreads();  // the previous scan's totals have been read
   if (lane == 63) wave_total[wave] = v;
   __syncthreads();
@@ -63,22 +54,6 @@ __device__ __forceinline__ long long rle_block_scan(long long v, long long *wave
   }
   carry += total;
   return v + before;
-}
-
-__device__ __forceinline__ int rle_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int rle_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int rle_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 __global__ __launch_bounds__(256) void rle_parse_kernel(const uint8_t *__restrict__ bytes, const int *__restrict__ lists,
@@ -192,8 +167,8 @@ __global__ __launch_bounds__(256) void rle_fill_kernel(const int *__restrict__ d
       y_lo = min(y_lo, y), y_hi = max(y_hi, y + 1), x_lo = min(x_lo, x), x_hi = max(x_hi, x + 1);
     }
   }
-  count = rle_wave_sum(count);
-  y_lo = rle_wave_min(y_lo), y_hi = rle_wave_max(y_hi), x_lo = rle_wave_min(x_lo), x_hi = rle_wave_max(x_hi);
+  count = wave_all_sum(count);
+  y_lo = wave_all_min(y_lo), y_hi = wave_all_max(y_hi), x_lo = wave_all_min(x_lo), x_hi = wave_all_max(x_hi);
   if ((tid & 63) == 0 && count > 0) {
     int *o = stats + d * RLE_STATS;
     atomicAdd(o + 0, count);
@@ -221,8 +196,8 @@ __global__ __launch_bounds__(256) void rle_column_scan_kernel(const uint8_t *__r
     col_count[(size_t)d * W + x] = nb;
   }
   const int left = area > 0 ? W - x : 0, right = area > 0 ? x + 1 : 0;
-  const int s_nb = rle_wave_sum(nb), s_area = rle_wave_sum(area);
-  const int m_top = rle_wave_max(top), m_bottom = rle_wave_max(bottom), m_left = rle_wave_max(left), m_right = rle_wave_max(right);
+  const int s_nb = wave_all_sum(nb), s_area = wave_all_sum(area);
+  const int m_top = wave_all_max(top), m_bottom = wave_all_max(bottom), m_left = wave_all_max(left), m_right = wave_all_max(right);
   if ((threadIdx.x & 63) == 0 && s_nb + s_area > 0) {
     int *o = totals + d * RLE_STATS;
     atomicAdd(o + 0, s_nb), atomicAdd(o + 1, s_area);
@@ -246,7 +221,7 @@ __global__ __launch_bounds__(256) void rle_compact_kernel(const uint8_t *__restr
   rle_block_scan(before, wave_total, carry);  // carry = boundaries of the columns left of this tile
   if (wave == 0) {
     const long long c = x0 + lane < W ? cc[x0 + lane] : 0;
-    col_base[lane] = begin + carry + rle_wave_scan(c, lane) - c;
+    col_base[lane] = begin + carry + wave_inclusive_sum(c, lane) - c;
   }
   for (int y0 = 0; y0 < H; y0 += 64) {
     __syncthreads();  // col_base written; the previous tile has been read

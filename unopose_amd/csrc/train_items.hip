@@ -117,22 +117,6 @@ __global__ __launch_bounds__(256) void items_view_rows_kernel(const float *__res
   }
 }
 
-__device__ __forceinline__ int item_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int item_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int item_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // one wavefront per view over its rows' records
 __global__ __launch_bounds__(64) void items_view_table_kernel(const int *__restrict__ rows, int H, int W, int *__restrict__ table) {
   const int v = blockIdx.x, lane = threadIdx.x;
@@ -142,8 +126,8 @@ __global__ __launch_bounds__(64) void items_view_table_kernel(const int *__restr
     n_full += r[0], n_vis += r[1], n_set += r[2];
     if (r[2] > 0) top = min(top, y), bottom = max(bottom, y + 1), left = min(left, r[3]), right = max(right, r[4]);
   }
-  n_full = item_wave_sum(n_full), n_vis = item_wave_sum(n_vis), n_set = item_wave_sum(n_set);
-  top = item_wave_min(top), bottom = item_wave_max(bottom), left = item_wave_min(left), right = item_wave_max(right);
+  n_full = wave_all_sum(n_full), n_vis = wave_all_sum(n_vis), n_set = wave_all_sum(n_set);
+  top = wave_all_min(top), bottom = wave_all_max(bottom), left = wave_all_min(left), right = wave_all_max(right);
   if (lane == 0) {
     int *o = table + (size_t)v * ITEM_TABLE;
     o[0] = n_full, o[1] = n_vis, o[2] = n_set, o[3] = top, o[4] = bottom, o[5] = left, o[6] = right, o[7] = 0;
@@ -313,8 +297,7 @@ __global__ __launch_bounds__(256) void items_points_kernel(const uint8_t *__rest
     const double dx = dr[3 * i + 0] - s_mean[0], dy = dr[3 * i + 1] - s_mean[1], dz = dr[3 * i + 2] - s_mean[2];
     far = fmax(far, sqrt((dx * dx + dy * dy) + dz * dz));
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) far = fmax(far, __shfl_xor(far, o, 64));
+  far = wave_all_fmax(far);
   if (lane == 0) s_red[wid] = far;
   __syncthreads();
   if (tid == 0) radius[pair] = fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
