@@ -328,7 +328,10 @@ int unopose_add_layernorm_strided(const void *a, int a_bf16, const void *b, int 
   if (rows == 0) return UNOPOSE_OK;
   dim3 grid((unsigned)((rows + 3) / 4));
   hipStream_t s = (hipStream_t)stream;
-  const bool vec4 = C % 4 == 0 && ld_out % 4 == 0;  // every model shape (C = 256, 768); the scalar form covers the rest
+  // four channels per access (16 bytes of fp32, 8 of bf16): every row of a, b and out must start on such a boundary, so the widths AND the
+  // base pointers count (an `out` column block may start at any column).  Every model shape (C = 256, 768); the scalar form covers the rest
+  auto aligned4 = [](const void *p, int bf16) { return reinterpret_cast<uintptr_t>(p) % (bf16 ? 8 : 16) == 0; };
+  const bool vec4 = C % 4 == 0 && ld_out % 4 == 0 && aligned4(a, a_bf16) && (!b || aligned4(b, b_bf16)) && aligned4(out, out_bf16);
 #define UNOPOSE_LN(AB, BB, HB, OB)                                                                                               \
   do {                                                                                                                           \
     if (vec4)                                                                                                                    \

@@ -497,7 +497,7 @@ int unopose_normalize_rows_bf16(const void *x, int x_bf16, long rows, int C, flo
 
 int unopose_transpose_pad_bf16(const void *v, long ld, int B, int m, int C, int pad, void *vt, unopose_stream_t stream) {
   UNOPOSE_REQUIRE(v && vt, "transpose_pad_bf16: null pointer");
-  UNOPOSE_REQUIRE(B >= 1 && m >= 1 && m <= pad && pad % 2 == 0 && pad <= 1024 && C % 64 == 0 && ld >= C, "transpose_pad_bf16: bad shape (m=%d pad=%d C=%d)", m, pad, C);
+  UNOPOSE_REQUIRE(B >= 1 && B <= 65535 && m >= 1 && m <= pad && pad % 2 == 0 && pad <= 1024 && C % 64 == 0 && ld >= C, "transpose_pad_bf16: bad shape (m=%d pad=%d C=%d)", m, pad, C);
   hipLaunchKernelGGL(transpose_pad_kernel, dim3(C / 64, B), dim3(256), (size_t)64 * (pad + 2) * 2, (hipStream_t)stream, (const u16 *)v, ld, m, C,
                      pad, (u16 *)vt);
   return check_launch("transpose_pad_bf16");
