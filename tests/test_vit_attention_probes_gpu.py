@@ -8,6 +8,7 @@ leave the bounds by 4x and more.
   bf16 (unopose_vit_attention)   vit_attn_kernel<1,1,4>  T < 512;  <2,2,4>  512 <= T < 1024;  vit_attn_kernel_dma<4>  T >= 1024;
                                  <2,2,8>  T >= 1024 with a qkv image of 2 GiB or more (test_two_gib_dispatch_boundary)
   fp32 class                     unopose_vit_attention_f32, _f32_split (attn_f32.hip), _f32_ss (vit_attn_f32s.hip)
+  (the stages all of them share: csrc/vit_attn_common.h)
 
 Each check prints `PROBE <kernel> T B H family worst err/bound` (pytest -s shows them)."""
 import os

@@ -10,7 +10,7 @@
 // query rows x four heads = the 16 rows of a v_mfma_f32_16x16x32_bf16 tile, so q k^T, the four per-row
 // (q W_p) E[n]^T products, the softmax (row == 16-lane DPP row) and P v all run on one set of
 // accumulators without touching HBM in between.
-#include "attn_common.h"  // (TA_NT / TA_MP, row16_max / row16_sum, zero8, wave_lds_handover)
+#include "attn_common.h"  // (TA_NT / TA_MP, row16_max / row16_sum, zero8)
 #include "gemm_common.h"  // (gemm_dma16: one 1-KiB LDS-DMA piece)
 
 namespace unopose {

@@ -1,5 +1,5 @@
 // What the bf16 (attn.hip) and the fp32-class (attn_f32.hip) token attention kernels share: the key-tile geometry their
-// callers size V^T, K^T and the saved P by, the softmax's 16-lane row reductions and the wave-local LDS hand-over.
+// callers size V^T, K^T and the saved P by, and the softmax's 16-lane row reductions.
 #pragma once
 #include "common.h"
 
@@ -36,13 +36,6 @@ __device__ __forceinline__ bf16x8 zero8() {
 #pragma unroll
   for (int i = 0; i < 8; ++i) z[i] = (__bf16)0.f;
   return z;
-}
-
-// A wave hands its own LDS writes to its own lanes (a staging buffer no other wave reads): release, wave barrier, acquire.
-__device__ __forceinline__ void wave_lds_handover() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 }  // namespace unopose

@@ -6,7 +6,8 @@
 // exact fp32 MFMA runs at 1/16 of the bf16 rate; instead every operand is split on the fly into
 // hi + lo bfloat16 parts and each product is issued as 3 bf16 MFMAs (a_hi b_hi + a_hi b_lo + a_lo b_hi,
 // fp32 accumulation): ~2^-16 relative error per product, i.e. fp32-class results at 5x the fp32 MFMA rate.
-#include "attn_common.h"  // (TA_NT / TA_MP, row16_sum / row16_max, zero8, wave_lds_handover)
+#include "attn_common.h"      // (TA_NT / TA_MP, row16_sum / row16_max, zero8)
+#include "vit_attn_common.h"  // (va_store_split: the split-layout output of vit_attn_f32_kernel<true>)
 
 namespace unopose {
 
@@ -463,25 +464,18 @@ __global__ __launch_bounds__(256) void vit_attn_f32_kernel(const float *__restri
 #pragma unroll
     for (int r = 0; r < 16; ++r) Ot[wave][col][t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb] = o[t][r] * inv;
   wave_lds_handover();
+  if (SPLIT) {
+    const size_t rowb = (size_t)H * 256;
+    va_store_split(Ot[wave], reinterpret_cast<char *>(out) + ((size_t)b * T + q0) * rowb + h * 256, rowb, T - q0, lane);
+    return;
+  }
   // 32 rows x 256 B: 16 lanes per row, 16 B each
 #pragma unroll
   for (int it = 0; it < 8; ++it) {
     const int row = it * 4 + (lane >> 4), seg = lane & 15;
     if (q0 + row < T) {
       const float4 v = *reinterpret_cast<const float4 *>(&Ot[wave][row][seg * 4]);
-      if (SPLIT) {
-        const int c = h * 64 + seg * 4;
-        uint2 hi, lo;
-        hi.x = cvt_pk_bf16_f32(v.x, v.y);
-        hi.y = cvt_pk_bf16_f32(v.z, v.w);
-        lo.x = cvt_pk_bf16_lo(v.x, v.y, hi.x);
-        lo.y = cvt_pk_bf16_lo(v.z, v.w, hi.y);
-        char *line = reinterpret_cast<char *>(out) + ((size_t)b * T + q0 + row) * (size_t)(H * 64) * 4 + (size_t)(c >> 5) * 128 + (c & 31) * 2;
-        *reinterpret_cast<uint2 *>(line) = hi;
-        *reinterpret_cast<uint2 *>(line + 64) = lo;
-      } else {
-        *reinterpret_cast<float4 *>(out + ((size_t)b * T + q0 + row) * (H * 64) + h * 64 + seg * 4) = v;
-      }
+      *reinterpret_cast<float4 *>(out + ((size_t)b * T + q0 + row) * (H * 64) + h * 64 + seg * 4) = v;
     }
   }
 }

@@ -212,6 +212,14 @@ __device__ __forceinline__ int lane_id() {
   return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
 }
 
+// Hand-over of LDS data between the lanes of ONE wavefront (a staging buffer no other wave reads): what the lanes wrote before it, every
+// lane may read after it.  Release, wave barrier, acquire.
+__device__ __forceinline__ void wave_lds_handover() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // sum / max over the 256 threads of a workgroup on the DPP family, `red`: 4 floats of LDS.  The barrier BEFORE the write lets calls
 // follow each other on the same `red`; there is none after the read.
 __device__ __forceinline__ float block_sum_256(float v, float *red /*[4]*/) {

@@ -16,13 +16,6 @@ namespace unopose {
 
 constexpr int LRF_SCAN_STEPS = 4;  // 64-candidate steps of the ball query per loop trip (measured against 1 step per trip)
 
-// Hand-over of LDS data between the lanes of ONE wavefront: what the lanes wrote before it, every lane may read after it.
-__device__ __forceinline__ void wave_lds_handover() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Float e of the cloud (N x 3, AoS) into its SoA slot.  The loop over e stays in the kernels, which differ in their thread counts: with the
 // loop in here too, the kernels' instruction streams no longer equal the ones their outputs were validated with.
 __device__ __forceinline__ void lrf_stage_coord(float *sx, float *sy, float *sz, int e, float v) {

@@ -9,40 +9,30 @@
 // double-buffered LDS by LDS-DMA (`buffer_load_dwordx4 ... lds`, 64 pieces of 1 KiB per chunk, per-lane source addresses pick the planes
 // apart; the K rows are XOR-swizzled on the SOURCE address, the V image is the [sub-tile][key][16 channels] form ds_read_b64_tr_b16
 // wants) -- no staging registers, no LDS stores, one counted wait + barrier per chunk; S^T = K Q^T with the operands swapped so that a
-// lane holds 16 keys of ONE query, deferred reference point + end-of-tile fix-up (vit_attn.hip), P from registers (split into hi / lo
+// lane holds 16 keys of ONE query, deferred reference point + end-of-tile fix-up (vit_attn_common.h), P from registers (split into hi / lo
 // there), three MFMAs per product (hi.hi + hi.lo + lo.hi, fp32 accumulation) in both contractions.
 // Round 4: 1293 us (8 waves, register-staged chunks) -> 1086 us at 64 images x 12 heads x 1374 tokens, same box.
-#include "common.h"
-#include "gemm_common.h"
+#include "vit_attn_common.h"
 
 namespace unopose {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int VS_CHUNK = 128;  // keys staged per LDS chunk (128, or 64: half the LDS, two workgroups per CU)
-constexpr int VS_KPLANE = VS_CHUNK * 128;  // bytes of a K plane [key][64 channels] bf16; 16-byte chunk c of row r sits at c ^ ((r >> 1) & 7)
-constexpr int VS_VSUBB = VS_CHUNK * 32 + 128;   // bytes per V sub-tile [128 keys][16 channels] (+ bank skew), 4 per plane
-constexpr int VS_VPLANE = 4 * VS_VSUBB;
-constexpr int VS_VOFF = 2 * VS_KPLANE;     // K hi | K lo | V hi | V lo
-constexpr int VS_BUFB = 2 * VS_KPLANE + 2 * VS_VPLANE;  // 66560 B
-constexpr float VS_DEFER = 8.f;  // log2 of the largest P the deferred rescale lets through
+// a chunk buffer: K hi | K lo (swizzled planes, VA_KPLANEB each) | V hi | V lo (V images, VA_VIMGB each)
+constexpr int VS_VOFF = 2 * VA_KPLANEB;
+constexpr int VS_BUFB = 2 * VA_KPLANEB + 2 * VA_VIMGB;  // 66560 B
 constexpr int VS_NW = 12;  // wavefronts per workgroup = 3 per SIMD (154 VGPRs); 8: 1189 us, 12: 1086 us at 64 x 12 x 1374
 
 // qkv_s: (B, T) token rows of 3 * H * 64 values in the split layout (3 * H * 256 bytes per token: q blocks | k blocks | v blocks,
 // head h = blocks 2h, 2h + 1 of each third); out_s: (B, T) rows of H * 64 values in the split layout.
 template <int NW>
-__global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s_kernel(const char *__restrict__ qkv_s, int T, int H,
-                                                                                                     int BH, int nq, float scale_log2e,
-                                                                                                     char *__restrict__ out_s) {
+__global__ __launch_bounds__(NW * 64, 1) void vit_attn_f32s_kernel(const char *__restrict__ qkv_s, int T, int H, int BH, int nq, float scale_log2e,
+                                                                   char *__restrict__ out_s) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   float (*Ot)[32][68] = reinterpret_cast<float (*)[32][68]>(smem);
   static_assert(NW * 32 * 68 * 4 <= 2 * VS_BUFB, "output staging must fit the chunk buffers");
   constexpr int NT = NW * 64;
   static_assert(NT == 384 || NT == 512 || NT == 768 || NT == 1024, "6, 8, 12 or 16 wavefronts per workgroup");
-  // workgroup -> (image, head, query block): all query blocks of one (image, head) share id % 8 (one XCD's L2 holds its K / V)
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int bh = (slot / nq) * 8 + xcd, qblk = slot % nq;
-  if (bh >= BH) return;
+  int bh, qblk;
+  if (!va_block(nq, BH, bh, qblk)) return;
   const int b = bh / H, h = bh % H;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int q0 = (qblk * NW + wave) * 32;
@@ -55,21 +45,21 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
   //      32 keys), 1 KiB each; wave w issues K pieces 4w .. 4w + 3 and V pieces 4w .. 4w + 3.  Rows past the image arrive as zeros.
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)smem;
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)((size_t)T * RB), 0x00020000);
-  constexpr int NPC = VS_CHUNK / 4, KP = VS_CHUNK / 8, VG = VS_CHUNK / 32;  // pieces of K (and of V) per chunk; K pieces / V key groups per plane
+  constexpr int NPC = VA_CHUNK / 4, KP = VA_CHUNK / 8, VG = VA_CHUNK / 32;  // pieces of K (and of V) per chunk; K pieces / V key groups per plane
   constexpr int NP = (NPC + NW - 1) / NW;  // pieces of K (and of V) per wave: piece ids wave, wave + NW, ... < NPC
   uint32_t kvo[NP], vvo[NP], kdst[NP], vdst[NP];
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const int kp = min(wave + i * NW, NPC - 1), p = kp / KP, rg = kp % KP;
-    const int krow = 8 * rg + (lane >> 3), gch = (lane & 7) ^ ((krow >> 1) & 7);
+    const int krow = 8 * rg + (lane >> 3), gch = va_kswz(lane & 7, krow);
     kvo[i] = (uint32_t)(krow * (int)RB + koff + (gch >> 2) * 128 + (gch & 3) * 16 + p * 64);
-    kdst[i] = (uint32_t)(p * VS_KPLANE + rg * 1024);
+    kdst[i] = (uint32_t)(p * VA_KPLANEB + rg * 1024);
     const int pv = kp / (4 * VG), sub = (kp / VG) & 3, kq = kp % VG, vkey = 32 * kq + (lane >> 1), ch = sub * 16 + (lane & 1) * 8;
     vvo[i] = (uint32_t)(vkey * (int)RB + voff + (ch >> 5) * 128 + (ch & 31) * 2 + pv * 64);
-    vdst[i] = (uint32_t)(VS_VOFF + pv * VS_VPLANE + sub * VS_VSUBB + kq * 1024);
+    vdst[i] = (uint32_t)(VS_VOFF + pv * VA_VIMGB + sub * VA_VSUBB + kq * 1024);
   }
   auto issue_chunk = [&](int c, int bslot) {
-    const uint32_t b0 = lds0 + bslot * VS_BUFB, ro = (uint32_t)(c * VS_CHUNK) * (uint32_t)RB;
+    const uint32_t b0 = lds0 + bslot * VS_BUFB, ro = (uint32_t)(c * VA_CHUNK) * (uint32_t)RB;
 #pragma unroll
     for (int i = 0; i < NP; ++i)
       if (wave + i * NW < NPC) gemm_dma16(b0 + kdst[i], kvo[i] + ro, rs, 0);  // (wave-uniform)
@@ -77,7 +67,7 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
     for (int i = 0; i < NP; ++i)
       if (wave + i * NW < NPC) gemm_dma16(b0 + vdst[i], vvo[i] + ro, rs, 0);
   };
-  const int nchunks = (T + VS_CHUNK - 1) / VS_CHUNK;
+  const int nchunks = (T + VA_CHUNK - 1) / VA_CHUNK;
   issue_chunk(0, 0);
   bf16x8_hl qf[4];
   {
@@ -91,7 +81,7 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
     }
   }
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(qf[ks].hi), "+v"(qf[ks].lo));  // the Q loads are complete HERE (see vit_attn.hip)
+  for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(qf[ks].hi), "+v"(qf[ks].lo));  // the Q loads are complete HERE (see va_wave_init)
   f32x16 o[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
@@ -99,11 +89,9 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
     for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
   float m_run = -3e38f, l_run = 0.f;
 
-  // this lane's slot in the transpose read: sub-tile (lane>>4)&1, key row 4 hb + ((lane&15)>>2), 8-byte chunk lane&3
-  const uint32_t vlane_off = (uint32_t)(VS_VOFF + ((lane >> 4) & 1) * VS_VSUBB + (4 * hb + ((lane & 15) >> 2)) * 32 + (lane & 3) * 8);
-  uint32_t kfo[4];  // K fragment of key row kt + col, k-step ks: 16-byte chunk 2 ks + hb, swizzled by the row
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) kfo[ks] = (uint32_t)(col * 128 + (((2 * ks + hb) ^ ((col >> 1) & 7)) << 4));
+  const uint32_t vlane_off = (uint32_t)(VS_VOFF + va_vlane_off(lane));
+  uint32_t kfo[4];
+  va_koff(col, hb, kfo);
 
   auto qk_tile = [&](const char *buf, int c0, int kt, bool partial, f32x16 &s) {
     // S^T = K Q^T: rows = 32 keys, cols = 32 queries
@@ -114,9 +102,9 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
     bf16x8_hl kf[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const char *kp = buf + kt * 128 + kfo[ks];
+      const char *kp = buf + kt * VA_KROWB + kfo[ks];
       kf[ks].hi = *reinterpret_cast<const bf16x8 *>(kp);
-      kf[ks].lo = *reinterpret_cast<const bf16x8 *>(kp + VS_KPLANE);
+      kf[ks].lo = *reinterpret_cast<const bf16x8 *>(kp + VA_KPLANEB);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -124,47 +112,22 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
     if (partial) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (c0 + kt + (r & 3) + 8 * (r >> 2) + 4 * hb >= T) s[r] = -3e38f;
+        if (c0 + kt + va_row(r) + 4 * hb >= T) s[r] = -3e38f;
     }
   };
   auto softmax_pv_tile = [&](const char *buf, int kt, f32x16 &s) {
     // the tile's V fragments are read before the softmax arithmetic (measured: each read in front of its MFMAs 1101 us, all fragments of a
     // product before its MFMAs 1086 us, the V fragments before the softmax 1079 us)
+    const char *vt = buf + vlane_off + kt * VA_VROWB;
     bf16x8_hl vfe[2][2];
-    {
-      const char *vl0 = buf + vlane_off;
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2)
+    for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const char *vp = vl0 + t * 2 * VS_VSUBB + (kt + s2 * 16) * 32;
-          union { bf16x8 v; s16x4 h4[2]; } vh, vl;
-          vh.h4[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp));
-          vh.h4[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + 8 * 32));
-          vl.h4[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + VS_VPLANE));
-          vl.h4[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + VS_VPLANE + 8 * 32));
-          vfe[s2][t] = bf16x8_hl{vh.v, vl.v};
-        }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // online softmax with the deferred reference point (vit_attn.hip): per-lane select, no branch before the P.V MFMAs
-    float mx = s[0];
-#pragma unroll
-    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
-    const auto sm = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-    mx = fmaxf(__uint_as_float(sm[0]), __uint_as_float(sm[1])) * scale_log2e;
-    const bool grow = mx > m_run + VS_DEFER;
-    const float m_use = grow ? mx : m_run;
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
-    m_run = m_use;
-    float ls = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      s[r] = __builtin_amdgcn_exp2f(fmaf(s[r], scale_log2e, -m_use));
-      ls += s[r];
-    }
-    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(ls), __float_as_uint(ls), false, false);
-    l_run = fmaf(l_run, alpha, __uint_as_float(sw[0]) + __uint_as_float(sw[1]));
+      for (int t = 0; t < 2; ++t) vfe[s2][t] = va_v_frag_hl(vt, s2, t);
+    __builtin_amdgcn_sched_barrier(0);
+    // online softmax with the deferred reference point: per-lane select, no branch before the P.V MFMAs
+    float alpha;
+    const bool grow = va_softmax(s, m_run, l_run, scale_log2e, alpha);
     // P = hi + lo, packed as the B operand of the two 16-key k-steps
     bf16x8_hl pf[2];
 #pragma unroll
@@ -174,39 +137,28 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
       for (int e = 0; e < 8; ++e) pv[e] = s[s2 * 8 + e];
       pf[s2] = split8_bf16(pv);
     }
-    const char *vlane = buf + vlane_off;
-    auto v_frag = [&](int s2, int t) {
-      const char *vp = vlane + t * 2 * VS_VSUBB + (kt + s2 * 16) * 32;
-      union {
-        bf16x8 v;
-        s16x4 h4[2];
-      } vh, vl;
-      vh.h4[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp));
-      vh.h4[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + 8 * 32));
-      vl.h4[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + VS_VPLANE));
-      vl.h4[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(vp + VS_VPLANE + 8 * 32));
-      return bf16x8_hl{vh.v, vl.v};
-    };
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
       for (int t = 0; t < 2; ++t) o[t] = mfma3_lh_hl_hh_32x32(vfe[s2][t], pf[s2], o[t]);
-    if (__builtin_expect(__any(grow), 0)) {  // rare after the first tile: O = (O - D) alpha + D with D = this tile's P.V (vit_attn.hip)
+    if (__builtin_expect(__any(grow), 0)) {  // rare after the first tile: O = (O - D) alpha + D with D = this tile's P.V
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         f32x16 d;
 #pragma unroll
         for (int r = 0; r < 16; ++r) d[r] = 0.f;
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) d = mfma3_lh_hl_hh_32x32(v_frag(s2, t), pf[s2], d);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[t][r] = fmaf(o[t][r] - d[r], alpha, d[r]);
+        for (int s2 = 0; s2 < 2; ++s2) d = mfma3_lh_hl_hh_32x32(va_v_frag_hl(vt, s2, t), pf[s2], d);
+        va_rereference(o[t], d, alpha);
       }
     }
   };
-  auto chunk_compute = [&](int c0, const char *buf) {
-    const int nk = min(VS_CHUNK, T - c0);
+
+  va_dma_chunks(nchunks, issue_chunk, [&](int c) {
+    if (!active) return;
+    const int c0 = c * VA_CHUNK, nk = min(VA_CHUNK, T - c0);
+    const char *buf = smem + (c & 1) * VS_BUFB;
     const int nt = (nk + 31) >> 5;  // tiles of this chunk; only the sequence's last one can be partial
     // (measured and not kept: the score MFMAs of tile t + 1 issued before the softmax of tile t -- slower at 3 waves / SIMD)
     for (int t = 0; t < nt; ++t) {
@@ -214,46 +166,17 @@ __global__ __launch_bounds__(NW * 64, VS_CHUNK == 64 ? 2 : 1) void vit_attn_f32s
       qk_tile(buf, c0, t * 32, (t + 1) * 32 > nk, s);
       softmax_pv_tile(buf, t * 32, s);
     }
-  };
-
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  for (int c = 0; c < nchunks; ++c) {
-    if (c + 1 < nchunks) issue_chunk(c + 1, (c + 1) & 1);  // (that buffer was last read in chunk c - 1, before the barrier that ended it)
-    if (active) chunk_compute(c * VS_CHUNK, smem + (c & 1) * VS_BUFB);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  }
+  });
   if (!active) return;
   // ---- normalise, transpose through LDS, store token rows in the split layout
   const float inv = 1.f / l_run;
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) Ot[wave][col][t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hb] = o[t][r] * inv;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  // 32 rows x 64 channels: 16 lanes per row, 4 channels each -> 8 bytes of hi and 8 bytes of lo
+    for (int r = 0; r < 16; ++r) Ot[wave][col][t * 32 + va_row(r) + 4 * hb] = o[t][r] * inv;
+  wave_lds_handover();
   const size_t ORB = (size_t)H * 256;
-#pragma unroll
-  for (int it = 0; it < 8; ++it) {
-    const int row = it * 4 + (lane >> 4), seg = lane & 15;
-    if (q0 + row < T) {
-      const float4 v = *reinterpret_cast<const float4 *>(&Ot[wave][row][seg * 4]);
-      uint2 hi, lo;
-      hi.x = cvt_pk_bf16_f32(v.x, v.y);
-      hi.y = cvt_pk_bf16_f32(v.z, v.w);
-      lo.x = cvt_pk_bf16_lo(v.x, v.y, hi.x);
-      lo.y = cvt_pk_bf16_lo(v.z, v.w, hi.y);
-      const int c = seg * 4;  // channel inside the head
-      char *line = out_s + ((size_t)b * T + q0 + row) * ORB + h * 256 + (c >> 5) * 128 + (c & 31) * 2;
-      *reinterpret_cast<uint2 *>(line) = hi;
-      *reinterpret_cast<uint2 *>(line + 64) = lo;
-    }
-  }
+  va_store_split(Ot[wave], out_s + ((size_t)b * T + q0) * ORB + h * 256, ORB, T - q0, lane);
 }
 
 }  // namespace unopose
@@ -266,15 +189,8 @@ int unopose_vit_attention_f32_ss(const void *qkv_split, int B, int T, int H, voi
   UNOPOSE_REQUIRE(qkv_split && out_split, "vit_attention_f32_ss: null pointer");
   UNOPOSE_REQUIRE(B >= 0 && T >= 1 && H >= 1 && (long)B * H * cdiv(T, 256) < (1L << 28), "vit_attention_f32_ss: bad sizes");
   if (B == 0) return UNOPOSE_OK;
-  constexpr int NW = VS_NW;
-  static bool opt[64];
-  const size_t lds = (size_t)2 * VS_BUFB;
-  if (lds_optin(opt, reinterpret_cast<const void *>(&vit_attn_f32s_kernel<NW>), lds, "vit_attention_f32_ss") != UNOPOSE_OK) return UNOPOSE_ELAUNCH;
-  const int BH = B * H, nq = cdiv(T, 32 * NW);
-  const long blocks = (long)cdiv(BH, 8) * nq * 8;
-  hipLaunchKernelGGL((vit_attn_f32s_kernel<NW>), dim3((unsigned)blocks), dim3(NW * 64), lds, (hipStream_t)stream, (const char *)qkv_split, T, H, BH,
-                     nq, 0.125f * 1.4426950408889634f, (char *)out_split);
-  return check_launch("vit_attention_f32_ss");
+  return va_launch<&vit_attn_f32s_kernel<VS_NW>, char, VS_NW, 32>("vit_attention_f32_ss", (size_t)2 * VS_BUFB, qkv_split, B, T, H, out_split,
+                                                                 (hipStream_t)stream);
 }
 
 }  // extern "C"
