@@ -378,6 +378,20 @@ int unopose_fine_assign(const void *f1, const void *f2, int B, int R, int C, int
 int unopose_min_dist(const float *p, const float *q, int B, int N, int M, const float *R,
                      const float *t, int cand_per_b, float *out, unopose_stream_t stream);
 
+/* Pose refinement: post_refinement (utils/model_utils.py:649-664; the reference ships it and never calls it) per pair, with
+ * the correspondences found anew in every iteration -- a trimmed, Cauchy-weighted ICP, the whole loop in one launch.
+ * p (B,N1,3) query cloud, q (B,N2,3) reference cloud, mask (B,N1) or NULL (non-zero: the point takes part), pose
+ * R_in (B,3,3) / t_in (B,3) with p ~ R q + t.  With prev = 0, for k < iters:
+ *   x_i = (p_i - t) R;  j_i = argmin_j |x_i - q_j|^2 (lowest j on ties), d_i = sqrt(min);  in_i = mask_i != 0 and d_i < tau;
+ *   c_k = sum in_i;  trace[b,k] = c_k;  stop if c_k <= prev or c_k < 3 (the rest of trace is -1);  prev = c_k;
+ *   w_i = in_i / (1 + (d_i / tau)^2);  (R, t) = weighted_procrustes(src = q_j, ref = p, w, thresh 0, eps 1e-5).
+ * R_out / t_out: the last pose (the input pose bit for bit when no iteration solved); trace (B,iters) int32, idx (B,N1) int32
+ * and dist (B,N1) or NULL: j and d of the last search that ran (-1 and inf when iters = 0).  One workgroup per pair, fixed
+ * reduction order (two calls agree bit for bit), no atomics.  N1 <= 4096, N2 <= 16384, B <= 65535, tau > 0. */
+int unopose_icp_refine(const float *p, const float *q, const float *mask, int B, int N1, int N2, const float *R_in,
+                       const float *t_in, float tau, int iters, float *R_out, float *t_out, int *trace, int *idx,
+                       float *dist, unopose_stream_t stream);
+
 /* coarse stage (:449-474): CDF of (a_ij w1_i w2_j)^1.5 into cdf_ws (B,(R-1)*(C-1)), then for
  * each of nprop hypotheses three searchsorted look-ups with rand (B,3*nprop), a 3-point
  * Procrustes (register Jacobi SVD) and the mean residual: Rout (B,nprop,9), tout (B,nprop,3),

@@ -51,6 +51,7 @@ SIGNATURES = {
     "unopose_bilinear_sample_compact": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P],
     "unopose_fine_assign": [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "unopose_min_dist": [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P],
+    "unopose_icp_refine": [_P, _P, _P, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P],
     "unopose_coarse_hypotheses": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
     "unopose_coarse_scores": [_P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P],
     "unopose_topk_smallest": [_P, _I, _I, _I, _P, _P],

@@ -93,6 +93,19 @@ def apply_overrides(cfg, overrides):
     return cfg
 
 
+def fine_matching_cfg(cfg):
+    """The ``fine_point_matching`` mapping the model is built from (``model.cfg`` where the config has one, else ``model``), created
+    when absent.  An override written as ``model.fine_point_matching.key=value`` beside a ``model.cfg`` is moved into it."""
+    model = cfg.setdefault("model", {})
+    if not isinstance(model, dict):
+        raise ValueError("config: model is not a mapping")
+    inner = model["cfg"] if isinstance(model.get("cfg"), dict) else model
+    fine = inner.setdefault("fine_point_matching", {})
+    if inner is not model and isinstance(model.get("fine_point_matching"), dict):
+        fine.update(model.pop("fine_point_matching"))
+    return fine
+
+
 def result_paths(cfg, iteration=None):
     """engine.py:37-52 -> (directory, csv path)."""
     cfg = Cfg(cfg)
@@ -205,6 +218,9 @@ def main(argv=None):
     ap.add_argument("--eval-device-off", action="store_true", help="with --eval: compute the pose errors on the host (same renders), for comparison")
     ap.add_argument("--vis", nargs="?", const="", default=None, metavar="DIR",
                     help="draw the saved estimates over the test images after saving (unopose_amd.vis_poses; rank 0, on its GPU); DIR defaults to vis/ beside the CSV")
+    ap.add_argument("--icp", nargs="?", const="10", default=None, metavar="ITERS",
+                    help="refine every fine pose against its two clouds by at most ITERS (default 10) iterations of ops.icp_refine: sets "
+                         "model.fine_point_matching.icp_iters (and icp_inlier_thres = 0.1 unless an override gives it)")
     ap.add_argument("--print-plan", action="store_true")
     ap.add_argument("opts", nargs="*", help="key=value overrides")
     args = ap.parse_args(argv)
@@ -212,7 +228,15 @@ def main(argv=None):
         ap.error("--device-masks requires --device-prep")
     if args.vis and "=" in args.vis:  # `--vis key=value`: an override, not a folder
         args.opts, args.vis = [args.vis] + list(args.opts), ""
+    if args.icp and "=" in args.icp:  # `--icp key=value`: an override, not a count
+        args.opts, args.icp = [args.icp] + list(args.opts), "10"
+    if args.icp is not None and not (args.icp.isdigit() and int(args.icp) >= 0):
+        ap.error(f"--icp: ITERS must be a non-negative integer, got {args.icp!r}")
     cfg = apply_overrides(load_config(args.config_file), args.opts)
+    fine = fine_matching_cfg(cfg)
+    if args.icp is not None:
+        fine["icp_iters"] = int(args.icp)
+        fine.setdefault("icp_inlier_thres", 0.1)
     out_dir, save_path = result_paths(cfg)
     c = Cfg(cfg)
     if args.eval and isinstance(cfg.get("bop_eval"), dict):  # an unknown error type stops the run here, before any GPU work
@@ -226,6 +250,8 @@ def main(argv=None):
                     device_prep=bool(args.device_prep), eval=bool(args.eval))
         if args.device_masks:
             plan.update(device_masks=True)
+        if int(fine.get("icp_iters", 0) or 0) > 0:
+            plan.update(icp_iters=int(fine["icp_iters"]), icp_inlier_thres=float(fine.get("icp_inlier_thres", 0.1)))
         if args.eval:
             from .bop_eval import dataset_paths
 

@@ -45,7 +45,10 @@ def default_model_cfg(**over):
         fine_point_matching=dict(nblock=3, input_dim=256, hidden_dim=256, out_dim=256, pe_radius1=0.1, pe_radius2=0.2,
                                  focusing_factor=3, temp=0.1, sim_type="cosine", normalize_feat=True,
                                  loss_predator_thres=0.15, loss_dis_thres=0.3, use_lrf=True, use_xyz=True,
-                                 nsample1=64, nsample2=256),
+                                 nsample1=64, nsample2=256,
+                                 # not in the reference's config: eval-time refinement of the fine pose by `ops.icp_refine` (0: off, the
+                                 # forward is unchanged); the threshold is post_refinement's own default, in radius-normalised units
+                                 icp_iters=0, icp_inlier_thres=0.1),
     )
     for k, v in over.items():
         if isinstance(v, dict) and isinstance(cfg.get(k), dict):

@@ -173,6 +173,7 @@ class FinePointMatchingOneRef(nn.Module):
         self.transformers = nn.ModuleList(
             [SparseToDenseTransformer(d, 4, cfg.focusing_factor) for _ in range(self.nblock)])
         self.taps = None  # assign a dict to receive (f1, f2, atten, score) of the next forward (tests)
+        self.icp_taps = None  # assign a dict to receive the refinement's operands and trace without leaving the fused pose head (tests)
 
     def forward_train(self, p1, f1, geo1, fps_idx1, p2, f2, geo2, fps_idx2, radius, end_points, pe_ahead=None):
         """Fi:58-117, training branch.  The positional encoding is evaluated per cloud, query first (its BatchNorm layers
@@ -237,7 +238,7 @@ class FinePointMatchingOneRef(nn.Module):
             sc = ops.score_head(f, self.score_heads[self.nblock - 1])
             o = ops.linear(f, self.out_proj)
             if self.taps is None and ops.fine_pose_fused_ok(o[:B], o[B:]):  # the similarity is never materialised
-                R, t, s = ops.fine_pose_from_features(o[:B], o[B:], self.cfg.temp, _scores(sc, n1, halves=True), p1, p2)
+                R, t, s = ops.fine_pose_from_features(o[:B], o[B:], self.cfg.temp, _scores(sc, n1, halves=True), p1, p2, **self._icp())
                 return self._finish(end_points, R, t, s, radius)
             scores = torch.cat((sc[:B], sc[B:]), dim=1)
             atten = ops.feature_similarity(o[:B], o[B:], self.cfg.temp)
@@ -257,14 +258,23 @@ class FinePointMatchingOneRef(nn.Module):
             scores = ops.score_head(torch.cat((f1, f2), dim=1), self.score_heads[self.nblock - 1])
             o1, o2 = ops.linear(f1, self.out_proj), ops.linear(f2, self.out_proj)
             if self.taps is None and ops.fine_pose_fused_ok(o1, o2):
-                R, t, s = ops.fine_pose_from_features(o1, o2, self.cfg.temp, _scores(scores, n1), p1, p2)
+                R, t, s = ops.fine_pose_from_features(o1, o2, self.cfg.temp, _scores(scores, n1), p1, p2, **self._icp())
                 return self._finish(end_points, R, t, s, radius)
             atten = ops.feature_similarity(o1, o2, self.cfg.temp)
         score = _scores(scores, n1)
         if self.taps is not None:
             self.taps.update(f1=f1, f2=f2, atten=atten, score=score)
-        R, t, s = ops.fine_pose(atten, score, p1, p2)
+        R, t, s = ops.fine_pose(atten, score, p1, p2, **self._icp())
         return self._finish(end_points, R, t, s, radius)
+
+    def _icp(self):
+        """The eval-time refinement of the fine pose (`ops.icp_refine`; cfg.icp_iters, default 0 = off) as the keywords of the pose head.
+        The unrefined pose, the operands and the trace go to `taps`, or to `icp_taps` where the route of the forward is to stay as it is."""
+        iters = int(self.cfg.get("icp_iters", 0) or 0)
+        if iters <= 0:
+            return {}
+        return dict(icp_iters=iters, icp_inlier_thres=float(self.cfg.get("icp_inlier_thres", 0.1)),
+                    taps=self.taps if self.taps is not None else self.icp_taps)
 
     @staticmethod
     def _finish(end_points, R, t, s, radius):

@@ -48,6 +48,7 @@ from .sampling import (  # noqa: F401
 from .pose import (  # noqa: F401
     overlap_scores, set_first_rows_, pose_score, rigid_rows, feature_similarity, soft_assignment, coarse_pose_torch, fine_pose_torch, _assign_labels, _check_score_width,
     coarse_pose, fine_pose, fine_pose_fused_ok, normalize_rows_bf16, normalize_rows_f32, fine_pose_from_features,
+    icp_refine, icp_refine_torch, _icp_args, _icp_stage,
 )
 from .prep import (  # noqa: F401
     PrepPlan, _desc_ints, _tap_table, prep_norm_table, _require, _result, prep_crop_resize, prep_lift, prep_gather,

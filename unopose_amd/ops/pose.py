@@ -227,10 +227,20 @@ def coarse_pose(atten, score, pts1, pts2, rand, n1p=6000, n2p=300):
     return R, t, pose_score
 
 
-def fine_pose(atten, score, pts1, pts2, dis_thres=0.15):
+def _icp_stage(pts1, pts2, R, t, w1, icp_iters, icp_inlier_thres, taps):
+    """The optional refinement between the fine head's Procrustes and its verification: (R, t) -> `icp_refine` over the points the head
+    matched (mask = w1 = label1 > 0).  `taps`: a dict that receives the unrefined pose, the operands and the trace."""
+    if taps is None:
+        return icp_refine(pts1, pts2, R, t, w1, icp_iters, icp_inlier_thres)
+    Rr, tr, trace, _, _ = icp_refine(pts1, pts2, R, t, w1, icp_iters, icp_inlier_thres, return_trace=True)
+    taps.update(icp_R0=R, icp_t0=t, icp_w1=w1, icp_p1=pts1, icp_p2=pts2, icp_trace=trace)
+    return Rr, tr
+
+
+def fine_pose(atten, score, pts1, pts2, dis_thres=0.15, icp_iters=0, icp_inlier_thres=0.1, taps=None):
     """compute_fine_Rt_overlap (model_utils.py:527-566) on HIP kernels: five streaming passes over the
     (B,N1+1,N2+1) similarity that write only O(N) statistics, weighted Procrustes (Jacobi), min-distance
-    verification."""
+    verification.  `icp_iters` > 0: the pose is refined by `icp_refine` before the verification, so the score is the refined pose's."""
     B, N1, _ = pts1.shape
     N2 = pts2.shape[1]
     atten, pts1, pts2 = _c(atten.float()), _c(pts1.float()), _c(pts2.float())
@@ -244,6 +254,8 @@ def fine_pose(atten, score, pts1, pts2, dis_thres=0.15):
         call("unopose_fine_correspondences", ptr(atten), B, N1 + 1, N2 + 1, ptr(score1), ptr(score2), ptr(stats),
              ptr(w1), ptr(w2), ptr(pts2), ptr(weight), ptr(pred), stream_ptr())
         R, t = weighted_procrustes(pred, pts1, weight, 0.001)
+        if icp_iters > 0:
+            R, t = _icp_stage(pts1, pts2, R, t, w1, icp_iters, icp_inlier_thres, taps)
         dis = torch.empty(B, N1, dtype=torch.float32, device=dev)
         call("unopose_min_dist", ptr(pts1), ptr(pts2), B, N1, N2, ptr(R), ptr(t), 1, ptr(dis), stream_ptr())
     return R, t, pose_score(dis, w1, dis_thres)
@@ -279,11 +291,11 @@ def normalize_rows_f32(f):
     return out
 
 
-def fine_pose_from_features(f1, f2, temp, score, pts1, pts2, dis_thres=0.15):
+def fine_pose_from_features(f1, f2, temp, score, pts1, pts2, dis_thres=0.15, icp_iters=0, icp_inlier_thres=0.1, taps=None):
     """compute_feature_similarity (cosine, /temp; model_utils.py:260-282) + compute_fine_Rt_overlap (:527-566) with the
     similarity recomputed tile by tile inside the three reduction passes instead of stored: f1 (B,N1+1,256), f2
     (B,N2+1,256) are the out_proj features (row 0 = background token).  Same bf16 operands / fp32 accumulation as the
-    autocast bmm of `feature_similarity`."""
+    autocast bmm of `feature_similarity`.  `icp_iters`, `icp_inlier_thres`, `taps`: as in `fine_pose`."""
     B, N1, _ = pts1.shape
     N2 = pts2.shape[1]
     assert f1.shape == (B, N1 + 1, 256) and f2.shape == (B, N2 + 1, 256)
@@ -301,6 +313,114 @@ def fine_pose_from_features(f1, f2, temp, score, pts1, pts2, dis_thres=0.15):
         call("unopose_fine_assign", ptr(a), ptr(b), B, R, C, 256, 1.0 / temp, ptr(score1), ptr(score2), ptr(pts2), ptr(ws),
              ptr(w1), ptr(w2), ptr(weight), ptr(pred), stream_ptr())
         Rm, t = weighted_procrustes(pred, pts1, weight, 0.001)
+        if icp_iters > 0:
+            Rm, t = _icp_stage(pts1, pts2, Rm, t, w1, icp_iters, icp_inlier_thres, taps)
         dis = torch.empty(B, N1, dtype=torch.float32, device=dev)
         call("unopose_min_dist", ptr(pts1), ptr(pts2), B, N1, N2, ptr(Rm), ptr(t), 1, ptr(dis), stream_ptr())
     return Rm, t, pose_score(dis, w1, dis_thres)
+
+
+ICP_MAX_N1, ICP_MAX_N2, ICP_MAX_B = 4096, 16384, 65535  # csrc/icp.hip: a pair's query points in one workgroup's registers, B on the grid
+
+
+def _icp_args(pts1, pts2, R, t, mask, iters, inlier_thres):
+    if pts1.dim() != 3 or pts2.dim() != 3 or pts1.shape[2] != 3 or pts2.shape[2] != 3 or pts1.shape[0] != pts2.shape[0]:
+        raise ValueError(f"icp_refine: pts1 (B, N1, 3) and pts2 (B, N2, 3) expected, got {tuple(pts1.shape)} and {tuple(pts2.shape)}")
+    B, N1, N2 = pts1.shape[0], pts1.shape[1], pts2.shape[1]
+    if tuple(R.shape) != (B, 3, 3) or tuple(t.shape) != (B, 3) or (mask is not None and tuple(mask.shape) != (B, N1)):
+        raise ValueError(f"icp_refine: R (B, 3, 3), t (B, 3) and mask (B, N1) expected for B = {B}, N1 = {N1}")
+    if N1 < 1 or N2 < 1 or int(iters) < 0 or not float(inlier_thres) > 0:
+        raise ValueError(f"icp_refine: N1 >= 1, N2 >= 1, iters >= 0 and inlier_thres > 0 expected, got {N1}, {N2}, {iters}, {inlier_thres}")
+    return B, N1, N2
+
+
+def icp_refine_torch(pts1, pts2, R, t, mask=None, iters=10, inlier_thres=0.1, return_trace=False):
+    """The rule of `icp_refine` as a composite of existing operators: one (B, N1, N2) distance matrix per coordinate and iteration, torch's
+    min over it, the HIP weighted Procrustes.  No host synchronisation either: a pair that has stopped is carried along unchanged.  The
+    baseline of scripts/icp_refine_rate.py and the route for tensors the kernel does not take (autograd recording, differentiable mode).
+    Distances and indices are the kernel's bit for bit (the same expressions, no contraction); the poses differ from it in the last bits
+    (another summation order in the Procrustes sums)."""
+    B, N1, N2 = _icp_args(pts1, pts2, R, t, mask, iters, inlier_thres)
+    iters, tau = int(iters), float(inlier_thres)
+    dev = pts1.device
+    with torch.autocast(dev.type, enabled=False):
+        p, q = pts1.float(), pts2.float()
+        R, t = R.float().clone(), t.float().clone()
+        live = torch.ones(B, N1, dtype=torch.bool, device=dev) if mask is None else mask != 0
+        prev = torch.zeros(B, dtype=torch.int64, device=dev)
+        active = torch.ones(B, dtype=torch.bool, device=dev)
+        trace = torch.full((B, iters), -1, dtype=torch.int32, device=dev)
+        idx = torch.full((B, N1), -1, dtype=torch.int32, device=dev)
+        dist = torch.full((B, N1), float("inf"), dtype=torch.float32, device=dev)
+        for k in range(iters):
+            a = p - t.unsqueeze(1)
+            x = (a[..., 0:1] * R[:, None, 0, :] + a[..., 1:2] * R[:, None, 1, :]) + a[..., 2:3] * R[:, None, 2, :]
+            e0 = x[:, :, None, 0] - q[:, None, :, 0]
+            e1 = x[:, :, None, 1] - q[:, None, :, 1]
+            e2 = x[:, :, None, 2] - q[:, None, :, 2]
+            d2 = (e0 * e0 + e1 * e1) + e2 * e2
+            d2 = torch.where(d2 < float("inf"), d2, torch.full_like(d2, float("inf")))  # (neither a NaN nor an infinity is taken)
+            m, j = d2.min(dim=2)  # (the first of equal minima)
+            d = torch.sqrt(m)
+            inl = live & (d < tau)
+            c = inl.sum(1)
+            trace[:, k] = torch.where(active, c, torch.full_like(c, -1)).to(torch.int32)
+            idx = torch.where(active[:, None], j.to(torch.int32), idx)
+            dist = torch.where(active[:, None], d, dist)
+            upd = active & (c > prev) & (c >= 3)
+            r = d / tau
+            w = torch.where(inl, 1.0 / (1.0 + r * r), torch.zeros_like(d))
+            src = torch.gather(q, 1, j.unsqueeze(2).expand(-1, -1, 3))
+            Rn, tn = weighted_procrustes(src, p, w, 0.0, 1e-5)
+            R = torch.where(upd[:, None, None], Rn, R)
+            t = torch.where(upd[:, None], tn, t)
+            prev = torch.where(upd, c, prev)
+            active = upd
+    return (R, t, trace, idx, dist) if return_trace else (R, t)
+
+
+def icp_refine(pts1, pts2, R, t, mask=None, iters=10, inlier_thres=0.1, return_trace=False):
+    """Refine the poses (R, t) of B pairs against their two clouds: a batched, trimmed, Cauchy-weighted ICP, the reference's
+    `post_refinement` (utils/model_utils.py:649-664) per pair with the nearest-neighbour correspondences found anew in every iteration.
+    One HIP launch (csrc/icp.hip: one workgroup per pair), fp32 whatever the autocast state, no host synchronisation.
+
+    pts1 (B, N1, 3) query cloud P, pts2 (B, N2, 3) reference cloud Q, mask (B, N1) or None (non-zero: the point takes part), R (B, 3, 3),
+    t (B, 3) with p ~ R q + t (the convention of `fine_pose`: (p - t) @ R maps P into Q's frame), tau = inlier_thres > 0, iters >= 0.
+    Per pair, in fp32, the expressions evaluated in this order without contraction:
+
+        prev = 0
+        for k in range(iters):
+            x_i  = ((p_i0 - t0) R[0][c] + (p_i1 - t1) R[1][c]) + (p_i2 - t2) R[2][c]        c = 0, 1, 2
+            j_i  = argmin_j ((x_i0 - q_j0)^2 + (x_i1 - q_j1)^2) + (x_i2 - q_j2)^2           lowest j on ties;  d_i = sqrt(minimum)
+            in_i = m_i != 0 and d_i < tau ;  c_k = sum in_i ;  trace[b, k] = c_k
+            if c_k <= prev or c_k < 3: break          (entries of trace after the break are -1; the pose stays as it is)
+            prev = c_k
+            w_i  = in_i / (1 + (d_i / tau)^2)
+            (R, t) = weighted_procrustes(src = q_{j_i}, ref = p_i, w, weight_thresh = 0, eps = 1e-5)
+
+    A pair with iters = 0, an all-zero mask or fewer than 3 inliers returns its input pose bit for bit.  NaN rows follow from the
+    comparisons as written (a NaN distance is never the minimum and never an inlier).  tests/icp_ref.py states the same rule in float64
+    numpy.  Returns (R, t), with `return_trace` (R, t, trace (B, iters) int32, idx (B, N1) int32, dist (B, N1)): j and d of the last
+    search that ran (-1 and inf when iters = 0).  N1 <= 4096, N2 <= 16384, B <= 65535, else ValueError.  Tensors the kernel does not take
+    (autograd recording) go through `icp_refine_torch`."""
+    B, N1, N2 = _icp_args(pts1, pts2, R, t, mask, iters, inlier_thres)
+    if N1 > ICP_MAX_N1 or N2 > ICP_MAX_N2 or B > ICP_MAX_B:
+        raise ValueError(f"icp_refine: N1={N1} N2={N2} B={B} exceed the limits N1 <= {ICP_MAX_N1}, N2 <= {ICP_MAX_N2}, B <= {ICP_MAX_B}")
+    if not _own_glue(pts1):
+        return icp_refine_torch(pts1, pts2, R, t, mask, iters, inlier_thres, return_trace)
+    p, q = _c(pts1.float()), _c(pts2.float())
+    Ri, ti = _c(R.float()), _c(t.float())
+    m = None if mask is None else _c(mask.float())
+    dev = p.device
+    Ro = torch.empty(B, 3, 3, dtype=torch.float32, device=dev)
+    to = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    trace = idx = dist = None
+    if return_trace:
+        trace = torch.empty(B, int(iters), dtype=torch.int32, device=dev)
+        idx = torch.empty(B, N1, dtype=torch.int32, device=dev)
+        dist = torch.empty(B, N1, dtype=torch.float32, device=dev)
+    with on_device(dev):
+        call("unopose_icp_refine", ptr(p), ptr(q), ptr(m) if m is not None else None, B, N1, N2, ptr(Ri), ptr(ti), float(inlier_thres), int(iters),
+             ptr(Ro), ptr(to), ptr(trace) if return_trace else None, ptr(idx) if return_trace else None, ptr(dist) if return_trace else None,
+             stream_ptr())
+    return (Ro, to, trace, idx, dist) if return_trace else (Ro, to)
