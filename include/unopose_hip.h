@@ -989,6 +989,16 @@ int unopose_items_points(const void *mask, const float *scene_depth, int H, int 
 int unopose_items_crops(const void *mask, const void *scene_rgb, int H, int W, const int *desc, int D, int max_h, int AW, void *atlas, void *packed,
                         unopose_stream_t stream);
 
+/* The scene stage of the online training pairs (unopose_amd/provider_online.py: sense_views_host is the specification; results equal it in
+ * every depth bit and colour byte): per view a textured background plane where the canvas is empty, then holes per cell and drop-outs at
+ * depth edges on the noise-free depth, then axial noise and disparity quantisation, all from the INPUT canvases, so out_depth / out_rgb
+ * must not be the inputs.  depth (V, H, W) float32 in model units (0 = nothing), rgb (V, H, W, 3) uint8; desc: unopose_scene_desc_words()
+ * 64-bit words per view (csrc/scene.hip documents the layout; a row of zero thresholds, zero noise, no steps and no plane passes its view
+ * through).  The caller has range-checked the descriptors.  One launch, no atomics. */
+int unopose_scene_desc_words(void);
+int unopose_scene_sense(const float *depth, const void *rgb, const void *desc, int V, int H, int W, float *out_depth, void *out_rgb,
+                        unopose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,11 @@ fine_npoint 2048, 224 x 224 crops, frozen backbone, fp32, `train.train_step_gate
             thread while step i runs
   resident  seconds per step on one batch that stays on the device
 
-    python scripts/online_pairs_rate.py [--models DIR] [--rounds 3] [--steps 10] [--out profiles/online_pairs_rate.txt]
+    python scripts/online_pairs_rate.py [--models DIR] [--rounds 3] [--steps 10] [--scene] [--out profiles/online_pairs_rate.txt]
+
+--scene adds a leg with the scene stage at its defaults (`dataloader.train.online.scene`: background plane, depth-sensor model) to `source` and
+`fed`, measured beside the scene-off leg in the same process, the two alternating round by round, and reports the stage's cost per batch; the
+output then goes to profiles/online_scene_rate.txt.
 
 Without --models, four ellipsoids (5120 faces each, vertex colours) are written to a temporary folder.  `fed` and `resident` alternate
 `--rounds` times in the same process; the spread is min - max of the rounds' means.  The aim: `fed` within `resident`'s own spread."""
@@ -75,8 +79,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--pairs", type=int, default=8)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "online_pairs_rate.txt"))
+    ap.add_argument("--scene", action="store_true", help="add the legs with the scene stage on, beside the scene-off ones")
+    ap.add_argument("--out", default=None, help="default: profiles/online_pairs_rate.txt, with --scene profiles/online_scene_rate.txt")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "online_scene_rate.txt" if args.scene else "online_pairs_rate.txt")
 
     import torch
 
@@ -97,6 +104,9 @@ def main():
     cfg = dict(img_size=224, n_sample_observed_point=2048, n_sample_template_point=5000, min_px_count_visib=512, min_visib_fract=0.1, dilate_mask=True,
                rgb_mask_flag=True, shift_range=0.01, online=dict(ONLINE_DEFAULTS))
     src = OnlinePairs(args.models or tmp.name, cfg, dev, seed=1, batch_size=args.pairs)
+    legs = [("", src)]
+    if args.scene:
+        legs.append(("+scene", OnlinePairs(args.models or tmp.name, dict(cfg, online=dict(ONLINE_DEFAULTS, scene={})), dev, seed=1, batch_size=args.pairs)))
     lines = ["online_pairs_rate: %d pairs, %d observed / %d template points, %d^2 crops, canvas %s, ssaa %d, %d models; %s" % (
         args.pairs, cfg["n_sample_observed_point"], cfg["n_sample_template_point"], cfg["img_size"], tuple(ONLINE_DEFAULTS["canvas"]), ONLINE_DEFAULTS["ssaa"],
         len(src.models), torch.cuda.get_device_name(dev))]
@@ -106,17 +116,23 @@ def main():
         lines.append(line)
 
     # -- the source alone
-    for i in range(2):
-        src.batch(i)
+    for _, source in legs:
+        for i in range(2):
+            source.batch(i)
     torch.cuda.synchronize()
-    rates = []
+    rates = {name: [] for name, _ in legs}
     for r in range(args.rounds):
-        t0 = time.perf_counter()
-        for i in range(args.steps):
-            src.batch(100 * r + i)
-            torch.cuda.synchronize()
-        rates.append(args.steps / (time.perf_counter() - t0))
-    say("source    %.1f batches/s (rounds: %s)" % (sum(rates) / len(rates), ", ".join("%.1f" % v for v in rates)))
+        for name, source in legs:
+            t0 = time.perf_counter()
+            for i in range(args.steps):
+                source.batch(100 * r + i)
+                torch.cuda.synchronize()
+            rates[name].append(args.steps / (time.perf_counter() - t0))
+    for name, _ in legs:
+        say("%-9s %.1f batches/s (rounds: %s)" % ("source" + name, sum(rates[name]) / len(rates[name]), ", ".join("%.1f" % v for v in rates[name])))
+    if args.scene:
+        cost = [1000.0 / on - 1000.0 / off for on, off in zip(rates["+scene"], rates[""])]
+        say("scene stage in the source: %.2f ms per batch (rounds: %s)" % (sum(cost) / len(cost), ", ".join("%.2f" % v for v in cost)))
 
     # -- the step, fed and resident, alternating
     torch.manual_seed(0)
@@ -135,13 +151,18 @@ def main():
         return (time.perf_counter() - t0) / args.steps
 
     fed, res = [], []
-    stream = src.iterate(1000)
-    next(stream)  # the first batch is not prefetched under a step
+    streams = [(name, source.iterate(1000), []) for name, source in legs]
+    for _, stream, _ in streams:
+        next(stream)  # the first batch is not prefetched under a step
     for _ in range(args.rounds):
-        fed.append(run(stream))
+        for _, stream, times in streams:
+            times.append(run(stream))
         res.append(run(iter(lambda: resident, None)))
-    stream.close()
-    say("fed       %.4f s/step (rounds: %s)" % (sum(fed) / len(fed), ", ".join("%.4f" % v for v in fed)))
+    for _, stream, _ in streams:
+        stream.close()
+    fed = streams[0][2]
+    for name, _, times in streams:
+        say("%-9s %.4f s/step (rounds: %s)" % ("fed" + name, sum(times) / len(times), ", ".join("%.4f" % v for v in times)))
     say("resident  %.4f s/step (rounds: %s)" % (sum(res) / len(res), ", ".join("%.4f" % v for v in res)))
     spread = max(res) - min(res)
     gap = sum(fed) / len(fed) - sum(res) / len(res)

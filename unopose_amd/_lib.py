@@ -186,6 +186,8 @@ SIGNATURES = {
     "unopose_items_views": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "unopose_items_points": [_P, _P, _I, _I, _P, _P, _P, _P, _D, _D, _D, _D, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "unopose_items_crops": [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P],
+    "unopose_scene_desc_words": [],
+    "unopose_scene_sense": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
 }
 
 

@@ -21,18 +21,13 @@
 // Crop descriptor, ITEM_CROP int32 per crop: 0 source view, 1 y0, 2 x0, 3 h, 4 w, 5 atlas row, 6 mask offset, 7 unused.
 // Pair constants, ITEM_PAIR float64 per pair: 0..8 spin (row-major), 9..11 shift.
 #include "common.h"
+#include "item_mix.h"
 
 namespace unopose {
 
 constexpr int ITEM_TABLE = 8, ITEM_DESC = 8, ITEM_CROP = 8, ITEM_PAIR = 12, ITEM_ROW = 5;
 constexpr int ITEM_MIN_KEPT = 32, ITEM_DILATE = 4, ITEM_ROUNDS = 6;
 constexpr double ITEM_DEPTH_TO_M = 0.001;
-
-__device__ __forceinline__ unsigned long long item_mix(unsigned long long z) {  // splitmix64's finaliser
-  z ^= z >> 30, z *= 0xbf58476d1ce4e5b9ull;
-  z ^= z >> 27, z *= 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
 
 // provider_online.draw_index: more than wanted -> a keyed bijection of [0, n_have) (balanced Feistel network over the next even number of
 // bits, walked until it lands inside: the walk ends, i itself is on the cycle); else a keyed hash modulo n_have

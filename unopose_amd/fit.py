@@ -23,7 +23,9 @@
   renders (query, reference) pairs of the folder's ``obj_XXXXXX.ply`` models on the rank's GPU and builds the items there (``dataloader.train.online.*``:
   canvas, focal, fill, offset, occluder_prob, ssaa, shading, ambient, max_chunks; the provider's fields still come from ``dataloader.train.dataset.cfg``).
   Batch i is a function of (seed, rank, i): ``--workers`` is ignored, ``--resume`` needs the iteration only.  ``--host`` builds the items with the numpy
-  rule from the renders read back (the same batches).  Off by default.
+  rule from the renders read back (the same batches).  Off by default.  ``--online-scene`` (or any ``dataloader.train.online.scene.KEY=VALUE``)
+  adds the scene stage of ``provider_online`` (part 4 of its docstring): a textured background plane behind the query and a depth-sensor
+  model on both views; without it the batches are the same bits as before the stage existed.
 * ranks: ``--gpus N`` starts N fresh processes before this one touches a GPU (RCCL through ``nccl``; ``gloo`` without GPUs); each runs
   ``freeze_backbone`` + ``wrap_ddp``.
 * rank 0 writes, into the output directory, ``model_{iteration:07d}.pth`` every ``period`` iterations (the newest ``max_to_keep`` are kept),
@@ -287,7 +289,8 @@ def run_settings(cfg, args, world=1):
                 load_from=args.load_from or cfg.get("misc", {}).get("load_from") or None,
                 device_crops=bool(args.device_crops or dl.get("device_crops", False)),
                 online_models=args.online_models or dl.get("online", {}).get("models") or None,
-                online_obj_ids=args.online_obj_ids or dl.get("online", {}).get("obj_ids") or None, online_host=bool(args.host))
+                online_obj_ids=args.online_obj_ids or dl.get("online", {}).get("obj_ids") or None, online_host=bool(args.host),
+                online_scene=bool(args.online_scene or dl.get("online", {}).get("scene") is not None))
 
 
 def _parser():
@@ -307,6 +310,9 @@ def _parser():
     ap.add_argument("--online-models", help="train on pairs rendered on the GPU from this folder of obj_XXXXXX.ply models (provider_online.OnlinePairs) "
                     "in place of the MegaPose files; also dataloader.train.online.models=DIR.  --workers is ignored")
     ap.add_argument("--online-obj-ids", type=int, nargs="*", help="with --online-models: these objects only (default: every model of the folder)")
+    ap.add_argument("--online-scene", action="store_true",
+                    help="with --online-models: a textured background plane behind the query and a depth-sensor model (holes, edge drop-outs, "
+                    "axial noise, disparity quantisation) on both views, at the defaults; dataloader.train.online.scene.KEY=VALUE sets single keys")
     ap.add_argument("--host", action="store_true", help="with --online-models: build the items with the numpy rule from the renders read back")
     ap.add_argument("--print-plan", action="store_true", help="resolve the settings, print them as JSON and stop (touches no GPU)")
     ap.add_argument("opts", nargs="*", help="key=value overrides")
@@ -362,6 +368,8 @@ def main(argv=None):
         from .provider_online import OnlinePairs
 
         online = dict(cfg["dataloader"]["train"].get("online", {}))
+        if s["online_scene"] and online.get("scene") is None:
+            online["scene"] = {}  # the stage at its defaults
         dataset = None
         loader = OnlinePairs(s["online_models"], dict(dc.get("cfg", dc), online=online), dev, s["seed"], rank=rank, world=world, host=s["online_host"],
                              batch_size=s["batch_size"], obj_ids=s["online_obj_ids"])

@@ -59,6 +59,29 @@ def item_views(obj_depth, obj_rgb, occ_depth, occ_rgb, occ_slot, dilate):
     return mask, scene_depth, scene_rgb, table
 
 
+def sense_views(depth, rgb, desc):
+    """The scene stage (csrc/scene.hip; `provider_online.sense_views_host` is the specification, equal in every depth bit and colour byte):
+    depth (V, H, W) float32 and rgb (V, H, W, 3) uint8 on the device, desc: V host descriptor rows (`provider_online.scene_rows`; range-checked
+    here) -> new (depth, rgb): per view the background plane where the canvas is empty, holes and edge drop-outs, axial noise and disparity
+    quantisation.  One launch for all views, enqueued on the current stream; nothing comes back to the host."""
+    from ..provider_online import SCENE_DESC, check_scene_rows
+
+    _require(depth, "sense_views: depth", torch.float32)
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise RuntimeError(f"sense_views: depth {tuple(depth.shape)} is not (V, H, W)")
+    V, H, W = (int(v) for v in depth.shape)
+    _require(rgb, "sense_views: rgb", torch.uint8, (V, H, W, 3))
+    desc = check_scene_rows(desc, H, W)
+    if len(desc) != V or V > 65535 or H * W >= 2 ** 31 or int(lib().unopose_scene_desc_words()) != SCENE_DESC:
+        raise ValueError(f"sense_views: {len(desc)} descriptors of {SCENE_DESC} words for {V} views of {H} x {W}")
+    dev = depth.device
+    desc_dev = torch.from_numpy(desc.view(np.int64)).to(dev)
+    out_depth, out_rgb = torch.empty_like(depth), torch.empty_like(rgb)
+    with on_device(dev):
+        call("unopose_scene_sense", ptr(depth), ptr(rgb), ptr(desc_dev), V, H, W, ptr(out_depth), ptr(out_rgb), stream_ptr(dev))
+    return out_depth, out_rgb
+
+
 def _windows(windows, H, W, max_side, what):
     """(y0, y1, x0, x1) or None per view -> (n, 5) integers y0, x0, h, w, valid, checked against the canvas and the scratch side."""
     out = np.zeros((len(windows), 5), dtype=np.int64)

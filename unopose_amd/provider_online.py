@@ -3,7 +3,7 @@
 (`OnlinePairs`; `python -m unopose_amd.fit --online-models DIR`).  No files, no loader workers: a batch is a pure function of
 (seed, rank, iteration).
 
-Three parts.
+Four parts.
 
 1. `draw_recipe(seed, rank, iteration, candidates, models, cfg, chunk=0)` draws everything random for `candidates` pairs from a private
    `np.random.Generator` over Philox, key = (seed, rank << 44 | iteration), counter word 3 = chunk; the global `np.random` is never touched.
@@ -21,7 +21,7 @@ Three parts.
    frac in [0.45, 0.75], on the ray to a point beside the query's centre: in a uniform direction, 0.4 to 1.0 times the mean of the two
    diameters away (at 1.0 the two bounding spheres would touch at equal depth; nearer to the camera the occluder looks larger and overlaps).
    Keys under `dataloader.train.online.*` and their defaults: `canvas` [H, W] = [240, 320]; `focal` = 300.0; `fill` = [0.35, 0.8];
-   `offset` = 0.6; `occluder_prob` = 0.5; `ssaa` = 2; `shading` = "phong"; `ambient` = 0.5; `max_chunks` = 8.
+   `offset` = 0.6; `occluder_prob` = 0.5; `ssaa` = 2; `shading` = "phong"; `ambient` = 0.5; `max_chunks` = 8; `scene` = None (part 4).
 
 2. `items_from_views_host(views, recipe, cfg)` is the item rule, `MegaPoseOneRefTrainSet.read_data` / `reference_view` restated on rendered
    canvases (colour (H, W, 3) uint8 and depth (H, W) float32 in model units of the reference, the query and the query's occluder, 0 =
@@ -54,7 +54,36 @@ Three parts.
    (chunk number `AUG_CHUNK`), per taken pair the query's 0.8 coin and plan, then the reference's; `ops.finish_crops` applies it.
    `host=True` reads the renders back and runs `items_from_views_host` and `ColorAugmentor.apply`: the same batch, tensor for tensor.
    Iterating from `start` prepares batch i + 1 on a side stream (`pipeline._pool_streams`) while step i runs, and hands a batch over with an
-   event and `record_stream`."""
+   event and `record_stream`.
+
+4. The scene stage, `dataloader.train.online.scene` (default None: absent, no launch, no draw, the batches above bit for bit; a dict, `{}`
+   included, turns it on): a textured background plane behind the query and a depth-sensor model on both views, between the renders and the
+   item rule.  Without it the rim of a dilated mask has depth 0 and lifts to the camera centre, which pulls the centroid towards the camera
+   by (rim share) x z and moves the keep sphere with it; MegaPose's images have the depth of whatever stands behind the object there.
+   `draw_scene` draws per candidate, from a generator of its own (chunk `SCENE_CHUNK0 + chunk`, so the recipe is the same with the stage on or
+   off): two view keys, the plane (unit normal n = (0, 0, -1) tilted by up to `plane_tilt` degrees about an in-image axis; point p0 on the ray
+   through the query's model centre at depth z_q + (0.5 + g) diameter, g uniform in `plane_gap`; two in-plane axes; a texture key).
+   `sense_views_host(depth, rgb, desc)` is the pixel rule, one descriptor row per view (`scene_rows`), float64 on metres with + - x / floor
+   rint and comparisons only, every stage reading the INPUT canvas, so no pixel waits for another's output; csrc/scene.hip equals it bit for
+   bit.  Random numbers are `_scene_hash(key, stream, index)` = mix(key ^ mix((stream << 40 | index) + gold)); probabilities are integer
+   thresholds on the hash's upper 32 bits.
+   * (a) background (a query with a plane, where the view has no depth): r = ((x - cx) / f, (y - cy) / f, 1), nr = (n0 rx + n1 ry) + n2,
+     z = (n . p0) / nr; nothing where nr >= 0 or z is outside (0, 10 m].  Colour: plane coordinates s, t = ((z r - p0) . u, v) / cell with
+     cell = `texture_cell` diameters; three octaves (s, t times 1, 2, 4; weights 0.5, 0.3, 0.2, added in that order) of value noise, the
+     lattice byte of channel c = byte c of hash(texture key, 3 + octave, (iu & 0xFFFFF) << 20 | iv & 0xFFFFF), blended
+     (b00 + (b10 - b00) fu, b01 + (b11 - b01) fu, then top + (bottom - top) fv); floor(x + 0.5).
+   * (b) drop-outs, decided on the noise-free depth after (a), for pixels with depth: the hole of cell (y // hole_cell, x // hole_cell)
+     (stream 0, index = the cell's row-major number, `hole_prob`); an edge pixel -- a 4-neighbour inside the canvas without depth or with
+     |z - z_n| > `edge_thres` z -- drops with `edge_drop` (stream 1, pixel number).  A dropped pixel gets depth 0 and keeps its colour.
+   * (c) on the others, when the noise or the quantisation is on: z <- z + (a + b (z - z0)^2) g with g = (the sum of the four 16-bit fields
+     of hash(key, 2, pixel) - 131070) sqrt(3) / 65536 (Irwin-Hall, unit variance, |g| <= 2 sqrt 3); no return (depth 0) if z <= 0; then with
+     `disparity_steps` s > 0 and fb = focal x `baseline_m`: k = rint((s fb) / z), no return if k < 1, z <- fb / (k / s); float32(z * 1000.0).
+   A pixel no stage touches keeps its input bits.  The references are sensed by (b), (c) before the item rule reads their depth; the
+   queries by (a), (b), (c) on the composed scene depth and colour, after the mask and the table are taken from the renders.
+   Keys under `online.scene.*`: `background` = "plane" (or "none"), `plane_gap` = [0.0, 1.5], `plane_tilt` = 35.0, `texture_cell` = 0.25,
+   `noise` = [0.0012, 0.0019, 0.4] (a, b, z0 of the Kinect axial model of Nguyen et al. 2012 as remembered: NOT pinned to the paper),
+   `baseline_m` = 0.075, `disparity_steps` = 8 (0: no quantisation), `edge_thres` = 0.03, `edge_drop` = 0.5, `hole_prob` = 0.01,
+   `hole_cell` = 6.  One occluder at most and no lateral or colour noise remain."""
 import os
 import os.path as osp
 
@@ -67,8 +96,18 @@ from .provider_train import AugPlan, ColorAugmentor, dilate_cross, pack_plans
 DEPTH_TO_M = 0.001
 MIN_KEPT = 32
 AUG_CHUNK = 2 ** 32 - 1
+SCENE_CHUNK0 = 2 ** 32  # the scene draw of recipe chunk c uses generator chunk SCENE_CHUNK0 + c: above every recipe chunk and AUG_CHUNK
 ONLINE_DEFAULTS = dict(canvas=(240, 320), focal=300.0, fill=(0.35, 0.8), offset=0.6, occluder_prob=0.5, ssaa=2, shading="phong", ambient=0.5,
-                       max_chunks=8)
+                       max_chunks=8, scene=None)
+# `noise`: sigma(z) = a + b (z - z0)^2 in metres, the shape of the Kinect axial model of Nguyen et al. 2012; the three constants are written
+# from memory and NOT pinned to the paper.
+SCENE_DEFAULTS = dict(background="plane", plane_gap=(0.0, 1.5), plane_tilt=35.0, texture_cell=0.25, noise=(0.0012, 0.0019, 0.4), baseline_m=0.075,
+                      disparity_steps=8, edge_thres=0.03, edge_drop=0.5, hole_prob=0.01, hole_cell=6)
+SCENE_DESC = 32  # 64-bit words per view descriptor (`scene_rows`)
+SCENE_Z_MAX_M = 10.0  # a background farther than this stays empty
+SCENE_OCTAVE_WEIGHTS = (0.5, 0.3, 0.2)
+SCENE_STREAM_HOLE, SCENE_STREAM_EDGE, SCENE_STREAM_NOISE, SCENE_STREAM_TEXTURE = 0, 1, 2, 3  # texture octave o: stream 3 + o
+SCENE_G_SCALE = 1.7320508075688772 / 65536.0  # sqrt(3) / 2^16: the sum of four 16-bit fields, centred, has variance (2^32 - 1) / 3
 _M64 = (1 << 64) - 1
 _GOLD_INT = 0x9E3779B97F4A7C15
 _GOLD = np.uint64(_GOLD_INT)
@@ -92,6 +131,27 @@ def online_cfg(cfg):
     if H < 2 or W < 2 or not 0 < lo <= hi <= 1 or not 0 <= float(out["offset"]) <= 1 or not 0 <= float(out["occluder_prob"]) <= 1:
         raise ValueError(f"dataloader.train.online: canvas {out['canvas']}, fill {out['fill']}, offset {out['offset']}, occluder_prob {out['occluder_prob']}")
     out["canvas"], out["fill"] = (H, W), (lo, hi)
+    out["scene"] = scene_cfg(out["scene"])
+    return out
+
+
+def scene_cfg(given):
+    """The `online.scene.*` keys with the defaults filled in; None (the stage is absent) stays None."""
+    if given is None:
+        return None
+    out = dict(SCENE_DEFAULTS)
+    unknown = sorted(set(given) - set(out))
+    if unknown:
+        raise ValueError(f"dataloader.train.online.scene: unknown keys {unknown}")
+    out.update({k: given[k] for k in given})
+    gap, noise = tuple(float(v) for v in out["plane_gap"]), tuple(float(v) for v in out["noise"])
+    steps, cell = int(out["disparity_steps"]), int(out["hole_cell"])
+    if (out["background"] not in ("plane", "none") or len(gap) != 2 or not 0 <= gap[0] <= gap[1] or not 0 <= float(out["plane_tilt"]) < 90
+            or not float(out["texture_cell"]) > 0 or len(noise) != 3 or min(noise[:2]) < 0 or not float(out["baseline_m"]) > 0
+            or steps != out["disparity_steps"] or not 0 <= steps < 2 ** 20 or float(out["edge_thres"]) < 0 or not 0 <= float(out["edge_drop"]) <= 1
+            or not 0 <= float(out["hole_prob"]) <= 1 or cell != out["hole_cell"] or cell < 1):
+        raise ValueError(f"dataloader.train.online.scene: {out}")
+    out.update(plane_gap=gap, noise=noise, disparity_steps=steps, hole_cell=cell)
     return out
 
 
@@ -238,6 +298,187 @@ def draw_recipe(seed, rank, iteration, candidates, models, cfg, chunk=0):
     return out
 
 
+# ---- the scene: a background plane and a depth-sensor model ---------------------------------------------------------------------------
+def draw_scene(seed, rank, iteration, candidates, recipe, models, cfg, chunk=0):
+    """Everything random of the scene stage for the `candidates` pairs of `recipe` (module docstring, part 4), from the generator
+    `recipe_generator(seed, rank, iteration, SCENE_CHUNK0 + chunk)`: `draw_recipe`'s stream is not touched.  Per candidate, whatever the
+    configuration says: two 64-bit view keys (query, reference); the plane's gap (uniform in `plane_gap`), tilt (uniform in [0, plane_tilt])
+    and tilt direction, the turn of its in-plane axes (both uniform in [0, 2 pi)); a 64-bit texture key.  All trigonometry happens here, in
+    float64.  -> dict of arrays with a leading `candidates` axis: keys (2,) uint64, plane (bool: the query has a background), n, p0, u, v
+    (3,) float64 in model units, camera frame (unit normal facing the camera, a point of the plane, two in-plane unit axes), cell (texture
+    cell in model units), tex_key uint64."""
+    sc = online_cfg(cfg)["scene"]
+    if sc is None:
+        raise ValueError("draw_scene: dataloader.train.online.scene is not set")
+    rng = recipe_generator(seed, rank, iteration, SCENE_CHUNK0 + int(chunk))
+    C = int(candidates)
+    out = dict(keys=np.zeros((C, 2), np.uint64), plane=np.full(C, sc["background"] == "plane"), n=np.zeros((C, 3)), p0=np.zeros((C, 3)),
+               u=np.zeros((C, 3)), v=np.zeros((C, 3)), cell=np.zeros(C), tex_key=np.zeros(C, np.uint64))
+    for k in range(C):
+        m = models[int(recipe["obj"][k])]
+        diam = float(m["diameter"])
+        keys = rng.integers(0, 2 ** 64, 2, dtype=np.uint64)
+        gap = rng.uniform(*sc["plane_gap"])
+        tilt, phi, psi = rng.uniform(0.0, np.deg2rad(float(sc["plane_tilt"]))), rng.uniform(0.0, 2 * np.pi), rng.uniform(0.0, 2 * np.pi)
+        tex_key = rng.integers(0, 2 ** 64, 1, dtype=np.uint64)[0]
+        centre = recipe["R_q"][k] @ np.asarray(m["centre"], dtype=np.float64) + recipe["t_q"][k]  # the query's model centre, z_q its depth
+        axis = np.array([np.cos(phi), np.sin(phi), 0.0])  # (0, 0, -1) turned by `tilt` about this in-image axis (Rodrigues; axis . n = 0)
+        n = np.array([-np.sin(phi) * np.sin(tilt), np.cos(phi) * np.sin(tilt), -np.cos(tilt)])
+        side = np.cross(n, axis)  # axis and side span the plane
+        for name, value in (("keys", keys), ("n", n), ("p0", centre * ((centre[2] + (0.5 + gap) * diam) / centre[2])),
+                            ("u", np.cos(psi) * axis + np.sin(psi) * side), ("v", np.cos(psi) * side - np.sin(psi) * axis),
+                            ("cell", float(sc["texture_cell"]) * diam), ("tex_key", tex_key)):
+            out[name][k] = value
+    return out
+
+
+def _threshold(prob):
+    """A probability as the integer threshold both routes compare the upper 32 bits of a hash with (`hash >> 32 < threshold`)."""
+    return int(np.rint(float(prob) * 2.0 ** 32))
+
+
+def scene_rows(scene, oc, which):
+    """The per-view descriptors of `sense_views_host` / `ops.sense_views`, (C, SCENE_DESC) uint64 words (floats are float64 bit patterns),
+    for the C queries (`which` = "query": key 0, the background plane where the pair has one), the C references ("reference": key 1, no
+    plane) or C views no stage touches ("off").  Words: 0 view key, 1 texture key, 2 plane (0 / 1), 3 hole threshold, 4 edge-drop threshold,
+    5 hole cell (pixels), 6 disparity steps, 7 unused; float64 from here: 8 9 10 the noise's a, b, z0, 11 focal x baseline (pixel metres),
+    12 edge threshold, 13-15 n, 16 n . p0 (metres), 17-19 p0 (metres), 20-22 u, 23-25 v, 26 texture cell (metres), 27 z_max (metres),
+    28 29 30 the camera's f, cx, cy, 31 unused."""
+    sc = oc["scene"]
+    C = len(scene["keys"])
+    H, W = oc["canvas"]
+    words, fl = np.zeros((C, SCENE_DESC), np.uint64), np.zeros((C, SCENE_DESC))
+    words[:, 5] = 1
+    fl[:, 11], fl[:, 13:16], fl[:, 26], fl[:, 27], fl[:, 28], fl[:, 29], fl[:, 30] = 1.0, (0.0, 0.0, -1.0), 1.0, SCENE_Z_MAX_M, float(oc["focal"]), W / 2.0, H / 2.0
+    if which != "off":
+        words[:, 0] = scene["keys"][:, 0 if which == "query" else 1]
+        words[:, 3], words[:, 4], words[:, 5], words[:, 6] = _threshold(sc["hole_prob"]), _threshold(sc["edge_drop"]), sc["hole_cell"], sc["disparity_steps"]
+        fl[:, 8:11], fl[:, 11], fl[:, 12] = sc["noise"], float(oc["focal"]) * float(sc["baseline_m"]), float(sc["edge_thres"])
+    if which == "query":
+        words[:, 1], words[:, 2] = scene["tex_key"], scene["plane"]
+        p0 = scene["p0"] * DEPTH_TO_M
+        fl[:, 13:16], fl[:, 17:20], fl[:, 20:23], fl[:, 23:26], fl[:, 26] = scene["n"], p0, scene["u"], scene["v"], scene["cell"] * DEPTH_TO_M
+        fl[:, 16] = (scene["n"][:, 0] * p0[:, 0] + scene["n"][:, 1] * p0[:, 1]) + scene["n"][:, 2] * p0[:, 2]
+    words[:, 8:31] = fl[:, 8:31].view(np.uint64)
+    return words
+
+
+def check_scene_rows(desc, H, W):
+    """Range-check descriptors for (H, W) canvases (both routes call this before they touch a pixel) -> (V, SCENE_DESC) uint64, contiguous."""
+    desc = np.ascontiguousarray(desc, dtype=np.uint64)
+    if desc.ndim != 2 or desc.shape[1] != SCENE_DESC:
+        raise ValueError(f"scene descriptors {desc.shape} are not (views, {SCENE_DESC})")
+    fl = desc.view(np.float64)
+    ints = desc[:, 2:7]
+    if (ints[:, 0] > 1).any() or (ints[:, 1:3] > 2 ** 32).any() or (ints[:, 3] < 1).any() or (ints[:, 3] > 2 ** 15).any() or (ints[:, 4] >= 2 ** 20).any():
+        raise ValueError("scene descriptors: plane flag, thresholds, hole cell or disparity steps out of range")
+    if not np.isfinite(fl[:, 8:31]).all() or (fl[:, 8:10] < 0).any() or (fl[:, 12] < 0).any() or (fl[:, [11, 26, 27, 28]] <= 0).any():
+        raise ValueError("scene descriptors: a constant is not finite or has the wrong sign")
+    # lattice coordinates stay inside the 20 bits the texture hash packs: |point - p0| <= z_max |r| + |p0|, the last octave scales by 4
+    reach = fl[:, 27] * np.sqrt(1.0 + ((W + np.abs(fl[:, 29])) / fl[:, 28]) ** 2 + ((H + np.abs(fl[:, 30])) / fl[:, 28]) ** 2) + np.linalg.norm(fl[:, 17:20], axis=1)
+    if ((desc[:, 2] == 1) & (4.0 * reach / fl[:, 26] >= 2.0 ** 19 - 2)).any():
+        raise ValueError("scene descriptors: the texture cell is too small for the reach of the background plane")
+    return desc
+
+
+def _scene_hash(key, stream, index):
+    """The random word of (view or texture key, stream number, pixel / cell / lattice index < 2^40): uint64 array."""
+    return _mix(np.uint64(key) ^ _mix((np.asarray(index).astype(np.uint64) | np.uint64(int(stream) << 40)) + _GOLD))
+
+
+def _scene_texture(tex_key, s, t):
+    """Three octaves of value noise at plane coordinates (s, t) (float64 arrays, in texture cells) -> (..., 3) uint8.  Octave o looks up the
+    lattice at (2^o s, 2^o t): the four corners' bytes (byte c of the hash of (texture key, stream 3 + o, corner) for channel c) are blended
+    along s, then along t; the octaves are weighted 0.5, 0.3, 0.2 and added in that order; floor(x + 0.5)."""
+    out = np.zeros(s.shape + (3,), np.uint8)
+    total = [None, None, None]
+    for o, weight in enumerate(SCENE_OCTAVE_WEIGHTS):
+        so, to = s * float(1 << o), t * float(1 << o)
+        fu_floor, fv_floor = np.floor(so), np.floor(to)
+        fu, fv = so - fu_floor, to - fv_floor
+        iu, iv = fu_floor.astype(np.int64), fv_floor.astype(np.int64)
+        corner = lambda du, dv: _scene_hash(tex_key, SCENE_STREAM_TEXTURE + o, (((iu + du) & 0xFFFFF) << 20) | ((iv + dv) & 0xFFFFF))  # noqa: E731
+        h00, h10, h01, h11 = corner(0, 0), corner(1, 0), corner(0, 1), corner(1, 1)
+        for c in range(3):
+            b00, b10, b01, b11 = (((h >> np.uint64(8 * c)) & np.uint64(255)).astype(np.float64) for h in (h00, h10, h01, h11))
+            top, bottom = b00 + (b10 - b00) * fu, b01 + (b11 - b01) * fu
+            value = (top + (bottom - top) * fv) * weight
+            total[c] = value if total[c] is None else total[c] + value
+    for c in range(3):
+        out[..., c] = np.floor(total[c] + 0.5).astype(np.uint8)
+    return out
+
+
+def sense_views_host(depth, rgb, desc, with_intermediates=False):
+    """The pixel rule of the scene stage (module docstring, part 4): depth (V, H, W) float32 in model units and rgb (V, H, W, 3) uint8 with
+    one descriptor row per view (`scene_rows`) -> new (depth, rgb).  with_intermediates: also a list with, per view, dict(z = the float64
+    depth in metres after the background and before drop-outs and noise, background, edge, dropped (bool masks), g (the unit noise))."""
+    depth, rgb = np.asarray(depth, dtype=np.float32), np.asarray(rgb, dtype=np.uint8)
+    V, H, W = depth.shape
+    if rgb.shape != (V, H, W, 3):
+        raise ValueError(f"sense_views_host: rgb {rgb.shape} for depth {depth.shape}")
+    desc = check_scene_rows(desc, H, W)
+    if len(desc) != V:
+        raise ValueError(f"sense_views_host: {len(desc)} descriptors for {V} views")
+    out_depth, out_rgb, infos = depth.copy(), rgb.copy(), []
+    ys, xs = np.mgrid[0:H, 0:W]
+    pix = ys * W + xs
+    for v in range(V):
+        w, fl = desc[v], desc[v].view(np.float64)
+        key, hole_thr, edge_thr, hole_cell, steps = w[0], np.uint64(w[3]), np.uint64(w[4]), int(w[5]), int(w[6])
+        a, b, z0, fb, edge_thres = fl[8:13]
+        raw = depth[v]
+        z = np.where(raw > 0, raw.astype(np.float64) * DEPTH_TO_M, 0.0)
+        # (a) the background plane where the view is empty
+        background = np.zeros((H, W), bool)
+        if int(w[2]):
+            f, cx, cy = fl[28:31]
+            rx, ry = (xs.astype(np.float64) - cx) / f, (ys.astype(np.float64) - cy) / f
+            nr = (fl[13] * rx + fl[14] * ry) + fl[15]
+            facing = ~(raw > 0) & (nr < 0.0)
+            zb = fl[16] / np.where(facing, nr, -1.0)
+            background = facing & (zb > 0.0) & (zb <= fl[27])
+            z = np.where(background, zb, z)
+            dx, dy, dz = rx * zb - fl[17], ry * zb - fl[18], zb - fl[19]
+            s = ((dx * fl[20] + dy * fl[21]) + dz * fl[22]) / fl[26]
+            t = ((dx * fl[23] + dy * fl[24]) + dz * fl[25]) / fl[26]
+            s, t = np.where(background, s, 0.0), np.where(background, t, 0.0)
+            out_rgb[v] = np.where(background[:, :, None], _scene_texture(w[1], s, t), rgb[v])
+        # (b) drop-outs on the noise-free depth: holes per cell, and edge pixels
+        surface = z > 0.0
+        cells = (ys // hole_cell) * ((W + hole_cell - 1) // hole_cell) + xs // hole_cell
+        dropped = surface & ((_scene_hash(key, SCENE_STREAM_HOLE, cells) >> np.uint64(32)) < hole_thr)
+        edge = np.zeros((H, W), bool)
+        for dy, dx in ((-1, 0), (1, 0), (0, -1), (0, 1)):
+            yy, xx = ys + dy, xs + dx
+            inside = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W)
+            zn = z[np.clip(yy, 0, H - 1), np.clip(xx, 0, W - 1)]
+            edge |= inside & (~(zn > 0.0) | (np.abs(z - zn) > edge_thres * z))
+        edge &= surface
+        dropped |= edge & ((_scene_hash(key, SCENE_STREAM_EDGE, pix) >> np.uint64(32)) < edge_thr)
+        # (c) axial noise, then disparity quantisation
+        h = _scene_hash(key, SCENE_STREAM_NOISE, pix)
+        fields = sum(((h >> np.uint64(16 * i)) & np.uint64(0xFFFF)).astype(np.int64) for i in range(4))
+        g = (fields - 131070).astype(np.float64) * SCENE_G_SCALE
+        sensed = surface & ~dropped
+        new = z
+        if a != 0.0 or b != 0.0 or steps:
+            new = z + (a + b * ((z - z0) * (z - z0))) * g
+            ok = new > 0.0  # noise below the camera plane: no return
+            if steps:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    k = np.rint((float(steps) * fb) / np.where(ok, new, 1.0))
+                    ok &= k >= 1.0  # less than one disparity step: beyond the sensor's range
+                    new = fb / (np.where(ok, k, 1.0) / float(steps))
+            new = np.where(ok, new, 0.0)
+            touched = sensed
+        else:
+            touched = sensed & background
+        out_depth[v] = np.where(dropped, np.float32(0), np.where(touched, (new * 1000.0).astype(np.float32), raw))
+        infos.append(dict(z=z, background=background, edge=edge, dropped=dropped, g=g))
+    return (out_depth, out_rgb, infos) if with_intermediates else (out_depth, out_rgb)
+
+
 # ---- the item rule -------------------------------------------------------------------------------------------------------------------
 def _extents(mask):
     """Half-open extents (top, bottom, left, right) of a mask; (H, 0, W, 0) when empty (the device table's convention)."""
@@ -273,30 +514,38 @@ def view_table_row(obj_depth, occ_depth, dilate):
     return mask, visible, front, row
 
 
-def items_from_views_host(views, recipe, cfg, with_intermediates=False):
+def items_from_views_host(views, recipe, cfg, with_intermediates=False, scene=None):
     """The item rule (module docstring, part 2).  views: ref_rgb, q_rgb, occ_rgb (C, H, W, 3) uint8 and ref_depth, q_depth, occ_depth
     (C, H, W) float32 (occluder canvases 0 where the pair has none).  -> a list of C entries: None for an invalid pair, else the
     `device_crops` form of the provider's item: pts, rgb_choose, translation_label, rotation_label, tem1_choose, tem1_pts, K and
     rgb_crop / rgb_cropmask, tem1_crop / tem1_cropmask (uint8 window crops of the scene colour and the window masks; `finish_item` turns
     them into rgb / tem1_rgb).  with_intermediates: (items, info) with info[k] = dict of every intermediate (tables, masks, scene, windows,
-    counts, radius, why an invalid pair is invalid)."""
+    counts, radius, why an invalid pair is invalid).  scene: `draw_scene`'s dict; the references' depth is then sensed (drop-outs, noise)
+    before anything reads it, and each query's composed scene depth and colour (background, drop-outs, noise) after its mask and table row
+    are taken from the renders: the mask stays the detector's, as the provider's is, and a hole inside it lifts to the camera centre."""
     oc = online_cfg(cfg)
     K = camera_matrix(oc)
     S, n_obs, n_tpl = int(_get(cfg, "img_size")), int(_get(cfg, "n_sample_observed_point")), int(_get(cfg, "n_sample_template_point"))
     use_dilation = bool(_get(cfg, "dilate_mask"))
     C = len(recipe["obj"])
     items, infos = [], []
+    ref_depth = views["ref_depth"]
+    if scene is not None:
+        ref_depth, _ = sense_views_host(ref_depth, views["ref_rgb"], scene_rows(scene, oc, "reference"))
+        q_rows = scene_rows(scene, oc, "query")
     for k in range(C):
         info = dict(valid=False, why=None)
         infos.append(info)
         items.append(None)
         # -- reference
-        rd = np.asarray(views["ref_depth"][k], dtype=np.float32)
+        rd = np.asarray(ref_depth[k], dtype=np.float32)
         r_mask, _, _, r_row = view_table_row(rd, np.zeros_like(rd), False)
         qd, cd = np.asarray(views["q_depth"][k], dtype=np.float32), np.asarray(views["occ_depth"][k], dtype=np.float32)
         q_mask, q_visible, front, q_row = view_table_row(qd, cd, use_dilation and bool(recipe["dilate"][k]))
         scene_depth = np.where(q_visible, qd, np.where(front, cd, np.float32(0))).astype(np.float32)
         scene_rgb = np.where(q_visible[:, :, None], views["q_rgb"][k], np.where(front[:, :, None], views["occ_rgb"][k], 0)).astype(np.uint8)
+        if scene is not None:
+            scene_depth, scene_rgb = (a[0] for a in sense_views_host(scene_depth[None], scene_rgb[None], q_rows[k:k + 1]))
         info.update(ref_row=r_row, q_row=q_row, ref_mask=r_mask, q_mask=q_mask, q_visible=q_visible, scene_depth=scene_depth, scene_rgb=scene_rgb)
         if r_row[2] == 0:
             info["why"] = "reference empty"
@@ -465,9 +714,10 @@ class OnlinePairs:
         return colour, depth, occ_colour, occ_depth
 
     # -- one chunk on the device
-    def chunk_device(self, recipe, canvases):
+    def chunk_device(self, recipe, canvases, scene=None):
         """The device form of `items_from_views_host` for one chunk -> dict(valid (C,) bool, windows, win_rows, tensors ...) with everything
-        per pixel and per point left on the device."""
+        per pixel and per point left on the device.  scene: `draw_scene`'s dict: `ops.sense_views` runs on the references before
+        `ops.item_views` and on the composed queries after it (the other half of the views passes through either launch unchanged)."""
         from . import ops
         from .ops.rle import _to_host
 
@@ -477,7 +727,12 @@ class OnlinePairs:
         use_dilation = bool(_get(self.cfg, "dilate_mask"))
         occ_slot = np.concatenate([np.where(recipe["occ"], np.arange(C), -1), np.full(C, -1)])
         dilate = np.concatenate([recipe["dilate"] & use_dilation, np.zeros(C, bool)])
+        if scene is not None:
+            off = scene_rows(scene, self.oc, "off")
+            depth, colour = ops.sense_views(depth, colour, np.concatenate([off, scene_rows(scene, self.oc, "reference")]))
         mask, scene_depth, scene_rgb, table = ops.item_views(depth, colour, occ_depth, occ_colour, occ_slot, dilate)
+        if scene is not None:
+            scene_depth, scene_rgb = ops.sense_views(scene_depth, scene_rgb, np.concatenate([scene_rows(scene, self.oc, "query"), off]))
         tab = _to_host(table)  # readback 1: counts and extents per view
         valid = np.zeros(C, bool)
         q_win, r_win = [None] * C, [None] * C
@@ -525,14 +780,17 @@ class OnlinePairs:
             for chunk in range(int(self.oc["max_chunks"])):
                 recipe = draw_recipe(self.seed, self.rank, iteration, self.B, self.models, self.cfg, chunk=chunk)
                 canvases = self.render_chunk(recipe)
+                scene = None
+                if self.oc["scene"] is not None:
+                    scene = draw_scene(self.seed, self.rank, iteration, self.B, recipe, self.models, self.cfg, chunk=chunk)
                 if self.host:
                     colour, depth, occ_colour, occ_depth = (t.cpu().numpy() for t in canvases)
                     C = self.B
                     views = dict(q_rgb=colour[:C], ref_rgb=colour[C:], q_depth=depth[:C], ref_depth=depth[C:], occ_rgb=occ_colour, occ_depth=occ_depth)
-                    res = items_from_views_host(views, recipe, self.cfg)
+                    res = items_from_views_host(views, recipe, self.cfg, scene=scene)
                     good = [k for k in range(C) if res[k] is not None]
                 else:
-                    res = self.chunk_device(recipe, canvases)
+                    res = self.chunk_device(recipe, canvases, scene=scene)
                     good = [int(k) for k in np.flatnonzero(res["valid"])]
                 taken += [(recipe, res, k) for k in good[:self.B - len(taken)]]
                 if len(taken) == self.B:
