@@ -900,6 +900,21 @@ int unopose_ref_select(const double *Rq, const long long *q_scene, const unsigne
                        const long long *c_scene, const unsigned long long *c_key, int C, const double *syms, int S, double trace_min,
                        unsigned long long seed, int cross_scene, int slab, long long *workspace, long long *out, unopose_stream_t stream);
 
+/* Potential symmetries of an object model (csrc/symmetry.hip; unopose_amd/model_sym.py's sym_deviation_host is the specification -- the
+ * project's own statement of the Hausdorff test behind bop_toolkit's symmetry annotations, which the toolkit itself does not compute).
+ * All float64, device memory.  pts (N,3): one cloud.  T (C,12): per candidate R (9, row-major) then t (3).
+ * out (C): the directed squared deviation  max_i min_j d2(T_c p_i, p_j)  with T_c p = dot3(R row, p) + t per component (bop_eval._dot3, then one
+ * add) and d2 = (dx*dx + dy*dy) + dz*dz without contraction: bit-equal to the host's value.  A candidate one of whose points has
+ * min_j d2 > bound2 is rejected: out[c] = +inf exactly (bound2 = +inf rejects nothing).  Every entry is written; what `out` held before does
+ * not matter.  The result does not depend on the tiling or on the order the workgroups run in; a rejected candidate stops its remaining
+ * query tiles of unopose_sym_deviation_tile() points.
+ * 1 <= N <= 2^22, 1 <= C <= 2^20, bound2 >= 0; more than unopose_sym_deviation_launch_candidates() candidates go out in several launches.
+ * The entry point checks sizes and pointers, not values: the caller hands over finite entries of magnitude <= 1e100 (ops.sym_deviation
+ * refuses anything else on the host).  With other values the result is arbitrary, but no access leaves the buffers. */
+int unopose_sym_deviation_tile(void);
+int unopose_sym_deviation_launch_candidates(void);
+int unopose_sym_deviation(const double *pts, int N, const double *T, int C, double bound2, double *out, unopose_stream_t stream);
+
 /* The optimiser step of the training run in three launches, whatever the number of tensors (csrc/optim.hip; unopose_amd/optim.py FusedAdam):
  * gradient hygiene (core/unopose/engine/engine_utils.py:14-18) + the 2-norm, then torch.nn.utils.clip_grad_norm_'s coefficient and a device-side
  * gate, then torch.optim.Adam's update (amsgrad = maximize = False).  fp32, contiguous tensors.  Device tables, built and range-checked by the caller:

@@ -174,6 +174,9 @@ SIGNATURES = {
     "unopose_ref_select_entry_tile": [],
     "unopose_ref_select_slab": [_I, _I, _I],
     "unopose_ref_select": [_P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _D, ctypes.c_ulonglong, _I, _I, _P, _P, _P],
+    "unopose_sym_deviation_tile": [],
+    "unopose_sym_deviation_launch_candidates": [],
+    "unopose_sym_deviation": [_P, _I, _P, _I, _D, _P, _P],
     "unopose_adam_table_ints": [_I],
     "unopose_adam_prepare": [_P, _P, _L, _I, _P, _P],
     "unopose_adam_finalise": [_P, _L, _I, _P, _P, _D, _D, _D, _D, _P, _P],

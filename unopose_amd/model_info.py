@@ -27,7 +27,7 @@ import sys
 import numpy as np
 
 INFO_KEYS = ("diameter", "min_x", "min_y", "min_z", "size_x", "size_y", "size_z")
-SYMMETRY_KEYS = ("symmetries_discrete", "symmetries_continuous")  # annotations: carried over, never computed
+SYMMETRY_KEYS = ("symmetries_discrete", "symmetries_continuous")  # annotations: carried over, never computed here (model_sym.py finds and writes them)
 PRUNE_MARGIN = 1.0 + 2.0 ** -40
 HOST_BLOCK = 1 << 21  # squared distances the host route forms at a time
 _PLY_NAME = re.compile(r"^obj_(\d{6})\.ply$")

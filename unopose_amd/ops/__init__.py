@@ -56,7 +56,7 @@ from .prep import (  # noqa: F401
 from .augment import AugTables, color_augment, finish_crops  # noqa: F401
 from .rle import pack_segs, rle_decode, rle_encode, window_masks  # noqa: F401
 from .items import item_crops, item_points, item_views, min_kept_points, sense_views  # noqa: F401
-from .score import vsd_counts, pose_errors, pose_metrics, adi, gt_visibility, pts_extent, ref_select  # noqa: F401
+from .score import vsd_counts, pose_errors, pose_metrics, adi, gt_visibility, pts_extent, ref_select, sym_deviation  # noqa: F401
 from .vis import compose_poses  # noqa: F401
 from .train import (  # noqa: F401
     _InfoNCEFn, infonce_two_way, _BNReLUTrain, bn_relu, _BNReLUMaxPoolTrain, bn_relu_maxpool, _SaliencyFn, saliency_pair,

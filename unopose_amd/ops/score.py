@@ -3,7 +3,8 @@
 `pose_metrics` (add, proj, re, te and the symmetry-aware projS, reS, teS) and `adi`; `gt_visibility` (csrc/gtinfo.hip) is the
 ground-truth side, the integers behind `scene_gt_info.json` and the two masks; `pts_extent` (csrc/modelinfo.hip) the model side, the box
 and the diameter behind `models_info.json`; `ref_select` (csrc/reftargets.hip) the reference-view search behind the one-reference target list
-(`ref_targets.select_host`, equal bits).  `bop_eval`'s and `gt_info`'s host functions are the
+(`ref_targets.select_host`, equal bits); `sym_deviation` (csrc/symmetry.hip) the Hausdorff deviation of a model under candidate
+symmetries (`model_sym.sym_deviation_host`, equal bits).  `bop_eval`'s and `gt_info`'s host functions are the
 specification: the counts equal numpy's, the distances and means agree with the BLAS-backed host code to rounding.
 
 The kernels trust the map indices they are given: the wrappers check every index against the map stacks on the host BEFORE
@@ -339,3 +340,31 @@ def ref_select(Rq, q_scene, q_key, Rc, c_scene, c_key, syms, trace_min, seed=0, 
              seed, int(bool(cross_scene)), slab, ptr(work), ptr(out), stream_ptr(dev))
     res = out.cpu().numpy()
     return res[0].copy(), res[1].copy(), res[2].copy(), res[3].copy().view(np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def sym_deviation_sizes():
+    """(query points per workgroup pass = points per LDS tile, candidates per launch) of the symmetry kernel."""
+    return int(lib().unopose_sym_deviation_tile()), int(lib().unopose_sym_deviation_launch_candidates())
+
+
+def sym_deviation(pts, transforms, bound=None, device="cuda"):
+    """`model_sym.sym_deviation_host` on the device (csrc/symmetry.hip).  pts (N, 3), 1 <= N <= 2^22; transforms (C, 4, 4) or (C, 3, 4) matrices
+    [R | t], 1 <= C <= 2^19; bound: a distance, None or inf for none -- host arrays, checked by `model_sym.check_inputs`, the host route's own
+    validator, before anything is launched (finite, |entry| <= 1e100).  The candidates and their inverses (`model_sym.inverse_transforms`, formed
+    on the host) go up with the points in one upload and through the kernel in one call.  -> (C,) float64 host array: sqrt(max(directed,
+    directed of the inverse)), +inf where either direction has a point further than `bound` from the cloud: the host route's bits.  Calling it
+    twice gives the same bits."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("sym_deviation: CPU not supported")
+    from ..model_sym import both_directions, check_inputs, two_sided  # one validator and one combination for both routes
+
+    p, R, t, bound2 = check_inputs(pts, transforms, bound)
+    table = both_directions(R, t)
+    N, C2 = len(p), len(table)
+    buf = torch.from_numpy(np.concatenate([p.reshape(-1), table.reshape(-1)])).to(dev)  # one upload
+    out = torch.empty(C2, dtype=torch.float64, device=dev)
+    with on_device(dev):
+        call("unopose_sym_deviation", ptr(buf), N, ptr(buf[3 * N:]), C2, bound2, ptr(out), stream_ptr(dev))
+    return two_sided(out.cpu().numpy())
