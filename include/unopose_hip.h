@@ -1014,6 +1014,33 @@ int unopose_scene_desc_words(void);
 int unopose_scene_sense(const float *depth, const void *rgb, const void *desc, int V, int H, int W, float *out_depth, void *out_rgb,
                         unopose_stream_t stream);
 
+/* Scoring class-agnostic mask proposals against one reference view per object (unopose_amd/match_dets.py states the rule in numpy;
+ * csrc/detmatch.hip).  No atomics: results depend on the inputs alone.
+ * _patch_valid: K square windows of 0 / 1 bytes back to back (the layout of unopose_window_masks; desc: per window its byte offset and its
+ *     side s, range-checked by the caller) -> out (K, (img_size / 14)^2) bytes: patch (r, c) of the resized window is 1 iff twice the set
+ *     pixels among its 14 x 14 reach 196, pixel (Y, X) reading window pixel (Y s / img_size, X s / img_size).  img_size a multiple of 14.
+ * _token_unit_rows: x (rows, D) bf16 (is_bf16 != 0) or fp32 -> out (rows, D) bf16 = x / |x| with the norm in fp32 and one rounding; a row
+ *     of norm 0 gives zeros.
+ * _patch_match_score: q_unit (P, T, D), r_unit (O, T, D) bf16 unit rows (16-byte aligned), q_valid (P, T), r_valid (O, T) bytes -> out (P, O):
+ *     the mean over the valid rows i of q[p] of the maximum over the valid rows j of r[o] of q[p][i] . r[o][j] (fp32 accumulation on the matrix
+ *     cores), 0 when either side has no valid row.  D a multiple of 32, T <= _patch_match_max_tokens().  The T x T products are never stored.
+ * _class_cosine: q_cls (P, D), r_cls (O, D) bf16 -> out (P, O) = q_cls[p] . r_cls[o] in fp32.
+ * _mask_pair_counts: masks (N, H, W) bytes, non-zero = set -> bits (N, ceil(H W / 64)) 64-bit words (scratch), area (N) and inter (N, N): the
+ *     pixel count of mask i AND mask j for two proposals of one category (the area on the diagonal), 0 across categories.
+ * _mask_nms_walk: one wavefront walks the proposals by (score descending, number ascending): a proposal is kept iff no kept proposal of its
+ *     category has (double)inter > nms_iou * (double)union with it, and keep[i] = 1 for the first max_per_object (0: all) kept ones of a
+ *     category.  A score that is not a number is never kept.  N <= _mask_nms_max_masks() in both. */
+int unopose_patch_valid(const void *packed, const int *desc, int K, int img_size, void *out, unopose_stream_t stream);
+int unopose_token_unit_rows(const void *x, int is_bf16, long rows, int D, void *out, unopose_stream_t stream);
+int unopose_patch_match_max_tokens(void);
+int unopose_patch_match_score(const void *q_unit, const void *q_valid, const void *r_unit, const void *r_valid, int P, int O, int T, int D, float *out,
+                              unopose_stream_t stream);
+int unopose_class_cosine(const void *q_cls, const void *r_cls, int P, int O, int D, float *out, unopose_stream_t stream);
+int unopose_mask_nms_max_masks(void);
+int unopose_mask_pair_counts(const void *masks, const int *category, int N, int H, int W, void *bits, int *area, int *inter, unopose_stream_t stream);
+int unopose_mask_nms_walk(const double *score, const int *category, const int *area, const int *inter, int N, double nms_iou, int max_per_object,
+                          void *keep, unopose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

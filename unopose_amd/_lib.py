@@ -191,6 +191,14 @@ SIGNATURES = {
     "unopose_items_crops": [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P],
     "unopose_scene_desc_words": [],
     "unopose_scene_sense": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "unopose_patch_valid": [_P, _P, _I, _I, _P, _P],
+    "unopose_token_unit_rows": [_P, _I, _L, _I, _P, _P],
+    "unopose_patch_match_max_tokens": [],
+    "unopose_patch_match_score": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "unopose_class_cosine": [_P, _P, _I, _I, _I, _P, _P],
+    "unopose_mask_nms_max_masks": [],
+    "unopose_mask_pair_counts": [_P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "unopose_mask_nms_walk": [_P, _P, _P, _P, _I, _D, _I, _P, _P],
 }
 
 

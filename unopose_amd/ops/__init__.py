@@ -7,6 +7,7 @@
     prep       query-side instance preparation of the BOP test provider (crops, clouds, pixel indices)
     augment    the training provider's colour augmentation for all crops of a batch, and the finishing of those crops behind it
     rle        COCO run-length masks: decode (with the depth restriction, count and extents), window crops, encode
+    detect     mask proposals against reference views: patch validity, unit token rows, the masked best-match patch score, mask suppression
     items      training items from rendered views: visible masks, counts and extents, points, pixel indices, crop atlas; the scene stage (provider_online)
     score      pose errors of the BOP'19 scorer (VSD counts, MSSD / MSPD) for many (estimate, ground truth) pairs per launch
     vis        per-image composition of the pose visualisation (nearest-pose layer, boxes, blend, depth-difference image)
@@ -55,6 +56,7 @@ from .prep import (  # noqa: F401
 )
 from .augment import AugTables, color_augment, finish_crops  # noqa: F401
 from .rle import pack_segs, rle_decode, rle_encode, window_masks  # noqa: F401
+from .detect import patch_valid, token_unit_rows, patch_match_score, class_cosine, mask_nms  # noqa: F401
 from .items import item_crops, item_points, item_views, min_kept_points, sense_views  # noqa: F401
 from .score import vsd_counts, pose_errors, pose_metrics, adi, gt_visibility, pts_extent, ref_select, sym_deviation  # noqa: F401
 from .vis import compose_poses  # noqa: F401
